@@ -8,10 +8,16 @@ lives in HBM (a torch-allocated uint8 tensor of 1-byte codes adopted by the
 library) before the
 timed region starts.  Synthetic by construction: the game is the input.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (driver contract), including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0
+(driver contract): the headline (value, ms_per_step) and the roofline figures that come
+from the timed steps' own HIP events.  --dump-outputs DIR then writes what the last
+timed solve returned (dump_outputs below).  --full adds everything that takes work of
+its own: the digest parity checks, the measured copy bandwidth, cpu_baseline and
+other_configs (--no-cpu-baseline and --no-toot leave those two out of a --full run).
+The line includes
   roofline      bound "hbm": achieved = the tier kernel's COMPULSORY bytes per
                 launch (1 B written + 2 producer-tier reads = 3 B per
                 position, x positions per launch) / its average launch time from
@@ -20,14 +26,15 @@ Prints ONE JSON line on rank 0 (driver contract), including
                 traffic_frac beside it; the SURVEY edge model (15.5 B/position) is
                 kept only as a diagnostic field, it is not an HBM bound for a
                 kernel that serves 6 of 14.5 child edges from LDS;
-  parity        the solved 2^32 table's gm_digest (all ranks summed) against the C
+  parity        the root's closed-form value; with --full the solved 2^32 table's
+                gm_digest (all ranks summed) against the C
                 oracle's digest of the same table -- live from the cpu_baseline
                 leg at N = 1, and the committed oracle value
                 (tests/golden/oracle_digests.json) at every N;
-  cpu_baseline  the C oracle's dense solver (oracle/gm_oracle.c), OpenMP over
+  cpu_baseline  (--full) the C oracle's dense solver (oracle/gm_oracle.c), OpenMP over
                 the host threads the box gives the process, on the full 2^32
                 workload (a 7-heap sample if the full one would exceed ~30 s);
-  other_configs config 3 (Toot-and-Otto 6x4) and config 4 (Othello 4x4) on the
+  other_configs (--full) config 3 (Toot-and-Otto 6x4) and config 4 (Othello 4x4) on the
                 sparse engine, hash-sharded over the same N ranks when N > 1,
                 each with its oracle digest check and (rank 0, N = 1) a CPU
                 baseline from the C oracle's sorted-layer OpenMP solver
@@ -598,6 +605,34 @@ def copy_bandwidth(torch, nbytes=1 << 31, reps=10):
     return gbs
 
 
+DUMP_SEED, DUMP_SAMPLE, DUMP_CHUNKS = 20240607, 1 << 22, 64
+
+
+def dump_outputs(path, torch, table, n, rec, rank, world):
+    """--dump-outputs: what the last timed solve handed its caller, as float .npy files
+    (about 50 MB in all).  gm_solve returns the position count and the root's record; the
+    solved table is the adopted tensor (2^32 one-byte codes in the engine's slot layout,
+    include/gmsolve.h gm_dense_table), too large to write whole, so it is written as
+      solve.npy               float64 [positions, root value, root remoteness]
+      table_sample_index.npy  float64, DUMP_SAMPLE slots drawn once from a fixed seed
+      table_sample.npy        float32, the codes in those slots
+      table_histogram.npy     float64 [DUMP_CHUNKS, 256]: how often each code occurs in
+                              each of DUMP_CHUNKS equal consecutive parts of the table,
+                              so every slot of the table bears on the dump.
+    The game is the input, so two runs with the same arguments write the same files.
+    At N > 1 every rank writes its own table (NAME_rankR.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    idx = np.random.default_rng(DUMP_SEED).integers(0, table.numel(), DUMP_SAMPLE, dtype=np.int64)
+    sample = table[torch.from_numpy(idx).to(table.device)].to(torch.float32).cpu().numpy()
+    hist = torch.stack([torch.bincount(c.to(torch.int32), minlength=256) for c in table.view(DUMP_CHUNKS, -1)])
+    np.save(os.path.join(path, "solve%s.npy" % sfx), np.array([n, rec >> 14, rec & 0x3FFF], dtype=np.float64))
+    np.save(os.path.join(path, "table_sample_index%s.npy" % sfx), idx.astype(np.float64))
+    np.save(os.path.join(path, "table_sample%s.npy" % sfx), sample)
+    np.save(os.path.join(path, "table_histogram%s.npy" % sfx), hist.cpu().numpy().astype(np.float64))
+
+
 def main():
     if os.environ.get("GM_BENCH_STACKS"):   # development: every rank's Python stacks on stderr after N s
         import faulthandler
@@ -607,6 +642,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--heaps", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the digest parity checks, the copy-bandwidth "
+                         "measurement, the CPU baseline and the side configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-toot", action="store_true", help="skip the config-3/4 side measurements")
     ap.add_argument("--cpu-heaps", type=int, default=8)
@@ -638,6 +678,8 @@ def main():
     ap.add_argument("--watchdog", type=float, default=None,
                     help="seconds before the headline solve is declared hung (default 240 + 2 s per step)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dist_owner == 1 and not args.dist_symmetry:
         ap.error("--dist-owner 1 needs --dist-symmetry 1 (the tier-balanced owner relies on the symmetric fill)")
 
@@ -826,11 +868,11 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [[round(float(x), 4) for x in a.tolist()] for a in allr]
 
-    # parity of the last timed solve: the whole table's digest (summed over ranks)
+    # parity of the last timed solve (--full): the whole table's digest (summed over ranks)
     # against the C oracle's digest of the same table
-    digest, ndig = summed_digest(ctx, world, dist, torch)
+    digest, ndig = summed_digest(ctx, world, dist, torch) if args.full else (None, None)
     rank_parity = None
-    if world > 1:
+    if world > 1 and args.full:
         d0, m0 = ctx.digest()
         mine = torch.tensor([d0 - (1 << 64) if d0 >= (1 << 63) else d0, m0], dtype=torch.int64, device=COLL_DEV)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -842,12 +884,16 @@ def main():
                                              args.dist_symmetry, args.dist_owner))
         barrier()
     watchdog.cancel()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, table, n, rec, rank, world)
     g = 0
     for i in range(args.heaps):
         g ^= ((root >> (4 * i)) & 15) % 3
     closed_form_ok = (rec >> 14) == (1 if g == 0 else 0)   # LOSS iff xor over heaps of (h mod 3) == 0
-    ref = committed_digest("subtract_%d" % args.heaps) if root == (1 << (4 * args.heaps)) - 1 else None
-    parity = {"digest": "%#018x" % digest, "positions_in_digest": ndig, "root_record": rec,
+    ref = (committed_digest("subtract_%d" % args.heaps)
+           if args.full and root == (1 << (4 * args.heaps)) - 1 else None)
+    parity = {"digest": None if digest is None else "%#018x" % digest, "positions_in_digest": ndig,
+              "root_record": rec,
               "root_closed_form_ok": closed_form_ok,
               "matches_committed_oracle_digest": (None if ref is None else
                                                   (digest, ndig, rec) == (ref["digest"], ref["positions"],
@@ -860,7 +906,7 @@ def main():
     st = ctx.stats()
     launches_per_solve = max(1, launches // max(1, args.steps))
     traffic_launch, traffic_solve = pmc_traffic(args.heaps)
-    copy_gbs = copy_bandwidth(torch) if world == 1 else None
+    copy_gbs = copy_bandwidth(torch) if (world == 1 and args.full) else None
     kernel_s_per_solve = kernel_ms / 1e3 / max(1, args.steps)
     avg_launch_s = (kernel_ms / 1e3) / max(1, launches)
     # algorithmic (compulsory) bytes per launch: 3 B x the positions this rank's launches solve
@@ -885,6 +931,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "strong",
@@ -946,7 +993,7 @@ def main():
         "rehearsal": ("--rehearse-one-gpu: %d ranks sharing ONE GPU (gloo for bench.py's collectives, IPC transport "
                       "for the halos); not a multi-GPU measurement" % world if args.rehearse_one_gpu else None),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"], live = cpu_baseline(args.cpu_heaps)
         if live is not None and args.heaps == args.cpu_heaps == 8 and root == 0xFFFFFFFF:
             parity["matches_live_oracle_digest"] = live == digest
@@ -954,7 +1001,7 @@ def main():
                         and parity["matches_live_oracle_digest"] is not False
                         and not (rank_parity and rank_parity["wrong_ranks"]))
     ctx.close()
-    if args.virtual_ranks == 1 and not args.no_toot:
+    if args.virtual_ranks == 1 and args.full and not args.no_toot:
         del table
         torch.cuda.empty_cache()
 
