@@ -489,6 +489,22 @@ int gm_expand_host_key(gm_ctx *h, const uint64_t *words, uint64_t *children, int
     *prim = d.primitive(k);
     *tier = d.tier(k);
     *n = *prim == UNDECIDED ? d.children(k, kids) : 0;
+    // the header promises the plugin's gen_moves order: squares x outer, y inner
+    // (othello_bit_new.py:163-166), where visit() walks the plane's lowest bit first.  The
+    // square played is the one bit the occupied plane gains: plane bit 63 - (8y + x).
+    auto rank = [&](const K128 &ch) {
+        const uint64_t placed = DescOthello8::occ(ch) ^ DescOthello8::occ(k);
+        if (!placed) return 0;   // the pass: a single child
+        const int j = 63 - __builtin_ctzll(placed);
+        return 8 * (j % 8) + j / 8;
+    };
+    for (int i = 1; i < *n; i++) {
+        const K128 ch = kids[i];
+        const int r = rank(ch);
+        int at = i;
+        for (; at > 0 && rank(kids[at - 1]) > r; at--) kids[at] = kids[at - 1];
+        kids[at] = ch;
+    }
     if (*n > cap) { set_error("children buffer holds %d, need %d", cap, *n); return GM_E_CAP; }
     if (children)
         for (int i = 0; i < *n; i++) DescOthello8::to_words(kids[i], children + (size_t)WIDE_WORDS * i);

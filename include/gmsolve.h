@@ -257,7 +257,9 @@ int gm_solve(gm_ctx *ctx, uint64_t root_key, uint64_t *n_positions, uint16_t *ro
  * virtual ranks, or one process per rank) and uses the *_key calls below; the one-word calls
  * return GM_E_ARG for it.  For one-word games the *_key calls equal their one-word forms.
  * gm_digest folds each key to one word first (mix64(lo ^ mix64(hi ^ c)) of the device key), so
- * digests compare across ranks and world sizes, not with one-word games. */
+ * digests compare across ranks and world sizes, not with one-word games.
+ * gm_expand_host_key returns the children in the plugin's gen_moves order (squares x outer, y
+ * inner, othello_bit_new.py:163-166; tests/test_oracle_othello8.py pins it to the plugin). */
 int gm_key_words(gm_ctx *ctx);
 int gm_pack_initial_key(gm_ctx *ctx, uint64_t *key_words);
 int gm_expand_host_key(gm_ctx *ctx, const uint64_t *key_words, uint64_t *children_words, int cap,

@@ -17,6 +17,17 @@ tests/golden/oracle_digests.json:
   subtract_8                     the 2^32-position synthetic game (config 5) by
                                  oracle_subtract_dense_mt + oracle_dense_digest.
 
+  othello_8x8_e12, othello_8x8_e14
+                                 the reference plugin's default 8x8 board from the 12- and
+                                 14-empty roots of the seed-5 playout (1,175,730 and 53.7 M
+                                 positions; 14 empties needs ~10 GB) by oracle/othello8.c,
+                                 which tests/test_oracle_othello8.py pins to the plugin's
+                                 own results (othello_8x8_playouts.npz, the 10-empty table,
+                                 othello_8x8_reference.json).  digest is the gm_digest form,
+                                 word_digest the layout-independent one of othello8_words.py.
+                                 e14 also writes othello_8x8_e14_sample.npz: 4,096 evenly
+                                 spaced entries of its table in key order.
+
 Existing entries are kept unless named on the command line.
 """
 import json
@@ -28,7 +39,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 from conftest import Oracle  # noqa: E402
+import othello8  # noqa: E402  (oracle/, on the path through conftest)
+import othello8_words as ow  # noqa: E402
 
 TOOT, SUB = 3, 5
 OUT = os.path.join(HERE, "oracle_digests.json")
@@ -52,7 +66,31 @@ def subtract(o, heaps):
     return {"positions": 1 << (4 * heaps), "digest": dg, "root_record": root}
 
 
+OTHELLO8_ROOTS = {"othello_8x8_e12": "30380028503841784646bfd6afc6be000200",    # tests/test_gpu_othello8.py ROOT12
+                  "othello_8x8_e14": "30300c2c503841784646b1d2afc6be000200"}    # tools/othello8_roots.py endgame_14
+OTHELLO8_SAMPLE = 4096
+
+
+def othello8_case(name):
+    root_hex = OTHELLO8_ROOTS[name]
+    sample = name == "othello_8x8_e14"
+    t = time.time()
+    r = othello8.Othello8Oracle().solve(ow.words_of(bytes.fromhex(root_hex).decode("latin-1")),
+                                        want=OTHELLO8_SAMPLE if sample else 0)
+    out = {"root_hex": root_hex, "positions": r["positions"], "per_tier": r["per_tier"],
+           "root_record": r["root_record"], "digest": r["digest"], "word_digest": r["word_digest"],
+           "seconds": round(time.time() - t, 1)}
+    if sample:
+        assert len(r["words"]) == OTHELLO8_SAMPLE
+        np.savez_compressed(os.path.join(HERE, name + "_sample.npz"), words=r["words"], records=r["records"],
+                            meta=json.dumps({"root_hex": root_hex, "positions": r["positions"],
+                                             "entries": "floor(i * positions / 4096) of the table in key order"}))
+    return out
+
+
 CASES = {
+    "othello_8x8_e12": lambda o: othello8_case("othello_8x8_e12"),
+    "othello_8x8_e14": lambda o: othello8_case("othello_8x8_e14"),
     "othello_4x4": lambda o: layered(o, 4, (4, 4)),
     "toot_4x4": lambda o: toot(o, 4, 4),
     "toot_5x4": lambda o: toot(o, 5, 4),

@@ -7,7 +7,11 @@ position is 2A + 16 = 144 bits; the rules are the plugin's own code, so the solv
 128-bit-key descriptor by their fingerprint (`graph=True` takes the
 explicit-graph path instead, tests/test_graph.py).  The golden table
 (tests/golden/othello_8x8_endgame.npz) is the canonical solution of the REFERENCE's plugin
-from the same root (tests/golden/make_golden.py --only othello8).
+from the same root (tests/golden/make_golden.py --only othello8).  Beyond this root the
+reference plugin's results are othello_8x8_playouts.npz (whole games) and
+othello_8x8_reference.json (12 empties and three pass roots), and the C oracle's are
+oracle_digests.json othello_8x8_e12 / _e14 with othello_8x8_e14_sample.npz
+(tests/test_oracle_othello8.py, tests/test_gpu_othello8.py).
 """
 import os
 
