@@ -48,7 +48,8 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_set_comm", "gm_solve", "gm_solve_graph", "gm_export", "gm_query", "gm_digest", "gm_stats",
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
-           "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout")
+           "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
+           "gm_histogram")
 
 
 class GMError(RuntimeError):
@@ -114,6 +115,7 @@ def lib():
         "gm_export": (ctypes.c_int, [vp, vp, vp, u64, P(u64)]),
         "gm_query": (ctypes.c_int, [vp, vp, vp, u64]),
         "gm_digest": (ctypes.c_int, [vp, P(u64), P(u64)]),
+        "gm_histogram": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int), P(u64)]),
         "gm_stats": (ctypes.c_int, [vp, P(Stats)]),
         "gm_tier_counts": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int)]),
         "gm_adopt_buffer": (ctypes.c_int, [vp, ctypes.c_int, vp, u64]),

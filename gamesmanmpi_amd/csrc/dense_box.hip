@@ -43,6 +43,7 @@
 // an f16 is a subnormal, ordered like the integer (the kernel keeps f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3).
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1800,6 +1801,17 @@ int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     *digest = hst[0];
     *n = hst[1];
     return GM_OK;
+}
+
+// census of the region's boxes (hist_common.hpp)
+int dense_box_histogram(Ctx *c, Hist *out) {
+    if (c->dist_box) return dist_box_histogram(c, out);
+    DenseBox *d = c->dbox;
+    CodeBins b;
+    GM_TRY(code_bins_begin(c, &b));
+    int rc = code_bins_launch<1>(c, &b, d->table, d->d_boxes, d->boxes.size(), 12, 8);
+    const int rc2 = code_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
 }
 
 int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {

@@ -33,6 +33,7 @@
 // on average).  The SURVEY §8d edge model charges 1 B per record and per child
 // edge: 1 + 14.5 = 15.5 B per position at 8 heaps (31 B with u16 records).
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -1235,6 +1236,17 @@ int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     *digest = h[0];
     *n = h[1];
     return GM_OK;
+}
+
+// census of the root's region: the table is one unit of 16^heaps bytes, slot = key
+int dense_sub_histogram(Ctx *c, Hist *out) {
+    if (c->dbox_active) return dense_box_histogram(c, out);
+    DenseSub *d = c->dsub;
+    CodeBins b;
+    GM_TRY(code_bins_begin(c, &b));
+    int rc = code_bins_launch<0>(c, &b, d->table, nullptr, 1, 4 * d->heaps, d->heaps);
+    const int rc2 = code_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
 }
 
 int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {

@@ -43,6 +43,7 @@
 // tables, enqueued by a host scheduler that interleaves the lists so that every cross-rank wait
 // comes after the record it waits for.
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1491,6 +1492,18 @@ int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     *digest = h[0];
     *n = h[1];
     return GM_OK;
+}
+
+// census of the same boxes: every virtual rank's, or this process's own
+int dist_box_histogram(Ctx *c, Hist *out) {
+    DistBox *d = c->dist_box;
+    CodeBins b;
+    GM_TRY(code_bins_begin(c, &b));
+    int rc = GM_OK;
+    for (auto &R : d->ranks)
+        if (R.table && rc == GM_OK) rc = code_bins_launch<1>(c, &b, R.table, R.d_boxes, R.boxes.size(), 12, 8);
+    const int rc2 = code_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
 }
 
 int dist_box_table(Ctx *c, void **p, uint64_t *bytes) {

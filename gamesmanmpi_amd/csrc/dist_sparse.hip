@@ -1356,6 +1356,29 @@ int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     return GM_OK;
 }
 
+// census of the tier tables of this context's ranks (its hash share in a multi-process solve)
+int dist_sparse_histogram(Ctx *c, Hist *out) {
+    ScoreBins b;
+    bool begun = false;
+    int rc = with_any_game(c, [&](const auto &desc) -> int {
+        using D = std::decay_t<decltype(desc)>;
+        auto *d = static_cast<DistSparseK<key_t<D>> *>(c->dist_sp);
+        size_t tiers = 0;
+        for (auto &R : d->ranks) tiers = std::max(tiers, R.tiers.size());
+        GM_TRY(score_bins_begin(c, (uint32_t)tiers + 1, &b));
+        begun = true;
+        for (auto &R : d->ranks)
+            for (auto &T : R.tiers)
+                if (T.count)
+                    hipLaunchKernelGGL(res_hist_kernel<D>, dim3(grid_counted(T.cap)), dim3(256), b.lds_bytes, c->stream,
+                                       desc, T.slots, T.cap, b.d, b.nbin, b.use_lds);
+        return GM_OK;
+    });
+    if (!begun) return rc;
+    const int rc2 = score_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
+}
+
 template <class D>
 static int query_ranks(Ctx *c, const D &desc, const key_t<D> *keys, uint16_t *recs, uint64_t n) {
     using K = key_t<D>;

@@ -60,6 +60,7 @@
 // sender's pack event; a host-side scheduler interleaves the lists so that every
 // cross-rank wait is enqueued after the record it waits for.
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 #include <mutex>
 
@@ -750,6 +751,20 @@ int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     *digest = h[0];
     *n = h[1];
     return GM_OK;
+}
+
+// census of the blocks the ranks own: a block is 16^low contiguous bytes of its rank's table
+int dist_sub_histogram(Ctx *c, Hist *out) {
+    DistSub *d = c->dist_sub;
+    CodeBins b;
+    GM_TRY(code_bins_begin(c, &b));
+    int rc = GM_OK;
+    for (auto &R : d->ranks) {
+        const uint32_t nb = R.off.back();
+        if (nb && rc == GM_OK) rc = code_bins_launch<0>(c, &b, R.table, R.dlist, nb, 4 * d->low, d->heaps);
+    }
+    const int rc2 = code_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
 }
 
 int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {

@@ -1,5 +1,6 @@
 // gm_api.hip -- the C ABI (include/gmsolve.h): contexts, dispatch, errors.
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 #include <chrono>
 #include <stdlib.h>
@@ -402,6 +403,7 @@ int gm_solve(gm_ctx *h, uint64_t root, uint64_t *n_positions, uint16_t *root_rec
     if (!key_valid(c, root)) { set_error("root key 0x%llx is not a valid position", (unsigned long long)root); return GM_E_KEY; }
     GM_HIP(hipSetDevice(c->device));
     c->solved = false;
+    c->hist_is_kept = false;
     int32_t launches = c->stats.kernel_launches;
     c->stats = gm_stats_t{};
     c->stats.kernel_launches = c->timing ? launches : 0;
@@ -523,6 +525,7 @@ int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16
     }
     GM_HIP(hipSetDevice(c->device));
     c->solved = false;
+    c->hist_is_kept = false;
     c->stats = gm_stats_t{};
     if (c->world > 1 && c->virtual_ranks > 1) {
         set_error("virtual ranks and a multi-process communicator are exclusive");
@@ -605,6 +608,7 @@ int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *o
         if (off[i + 1] < off[i]) { set_error("child_off is not monotone at %llu", (unsigned long long)i); return GM_E_ARG; }
     GM_HIP(hipSetDevice(c->device));
     c->solved = false;
+    c->hist_is_kept = false;
     c->stats = gm_stats_t{};
     c->stats.world = 1;
     GM_TRY(graph_solve(c, n, prim, off, kid));
@@ -659,6 +663,40 @@ int gm_digest(gm_ctx *h, uint64_t *digest, uint64_t *n) {
     if (c->engine == GM_ENGINE_DIST_DENSE) return dist_sub_digest(c, digest, n);
     if (c->engine == GM_ENGINE_DIST_SPARSE) return dist_sparse_digest(c, digest, n);
     return sparse_digest(c, digest, n);
+}
+
+int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) {
+    GM_TRY(need_solved(h));
+    if (!n_rem || !n || (counts && cap < 0)) return GM_E_ARG;
+    Ctx *c = &h->c;
+    GM_HIP(hipSetDevice(c->device));
+    Hist H;
+    if (counts && c->hist_is_kept) {
+        // the census of the counts == NULL query just before: one pass over the table per pair
+        for (int v = 0; v < 3; v++) H.v[v].swap(c->hist_kept[v]);
+    } else {
+        int rc;
+        if (c->engine == GM_ENGINE_GRAPH) rc = graph_histogram(c, &H);
+        else if (c->engine == GM_ENGINE_DENSE)
+            rc = c->game == GM_GAME_SUBTRACT ? dense_sub_histogram(c, &H) : small_dense_histogram(c, &H);
+        else if (c->engine == GM_ENGINE_DIST_DENSE) rc = dist_sub_histogram(c, &H);
+        else if (c->engine == GM_ENGINE_DIST_SPARSE) rc = dist_sparse_histogram(c, &H);
+        else rc = sparse_histogram(c, &H);
+        if (rc != GM_OK) return rc;
+    }
+    c->hist_is_kept = false;
+    const int nr = (int)H.n_rem();
+    *n_rem = nr;
+    *n = H.total();
+    if (!counts) {
+        for (int v = 0; v < 3; v++) c->hist_kept[v].swap(H.v[v]);
+        c->hist_is_kept = true;
+        return GM_OK;
+    }
+    if (cap < nr) { set_error("histogram buffer holds %d remoteness columns, need %d", cap, nr); return GM_E_CAP; }
+    for (int v = 0; v < 3; v++)
+        for (int r = 0; r < cap; r++) counts[(size_t)v * cap + r] = (size_t)r < H.v[v].size() ? H.v[v][r] : 0;
+    return GM_OK;
 }
 
 int gm_stats(gm_ctx *h, gm_stats_t *out) {

@@ -60,6 +60,7 @@ struct DistSub;
 struct DistBox;
 struct DistSparse;
 struct Graph;
+struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
 
 struct Ctx {
     int game = 0;
@@ -115,6 +116,9 @@ struct Ctx {
     uint16_t root_record = REC_UNSOLVED;
     gm_stats_t stats{};
     std::vector<uint64_t> tier_counts;
+    // gm_histogram: the census a counts == NULL query computed, kept for the fill call that follows
+    std::vector<uint64_t> hist_kept[3];
+    bool hist_is_kept = false;
 
     // device buffer cache (dev_alloc / dev_free)
     std::vector<std::pair<void *, uint64_t>> buf_live, buf_cache;
@@ -139,6 +143,7 @@ int dense_sub_solve(Ctx *c, uint64_t root);
 int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dense_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int dense_sub_histogram(Ctx *c, Hist *out);
 void dense_sub_free(Ctx *c);
 int dense_sub_table(Ctx *c, void **p, uint64_t *bytes);
 // the box-tiled engine for 8 heaps (dense_box.hip), reached through dense_sub_*
@@ -146,6 +151,7 @@ int dense_box_solve(Ctx *c, uint64_t root);
 int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dense_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int dense_box_histogram(Ctx *c, Hist *out);
 int dense_box_table(Ctx *c, void **p, uint64_t *bytes);
 void dense_box_free(Ctx *c);
 // shared with the split box engine (dist_box.hip)
@@ -177,6 +183,7 @@ int dist_box_solve(Ctx *c, uint64_t root);
 int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dist_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int dist_box_histogram(Ctx *c, Hist *out);
 int dist_box_table(Ctx *c, void **p, uint64_t *bytes);
 int dist_box_rank_stats(Ctx *c, double *kernel_ms, uint64_t *boxes, uint64_t *recv_bytes, int cap, int *n);
 int dist_box_op_ms(Ctx *c, int rank, double *ms, int cap, int *n);
@@ -200,6 +207,7 @@ int dist_sub_solve(Ctx *c, uint64_t root);
 int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int dist_sub_histogram(Ctx *c, Hist *out);
 void dist_sub_free(Ctx *c);
 int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what, int axis, uint32_t *off,
                   uint64_t off_cap, uint64_t *n_off, uint32_t *data, uint64_t data_cap, uint64_t *n_data);
@@ -213,24 +221,28 @@ int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n)
 int dist_sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dist_sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int dist_sparse_histogram(Ctx *c, Hist *out);
 void dist_sparse_free(Ctx *c);
 
 int small_dense_solve(Ctx *c, uint64_t root);
 int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int small_dense_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int small_dense_histogram(Ctx *c, Hist *out);
 void small_dense_free(Ctx *c);
 
 int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid);
 int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int graph_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int graph_histogram(Ctx *c, Hist *out);
 void graph_free(Ctx *c);
 
 int sparse_solve(Ctx *c, uint64_t root);
 int sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n);
+int sparse_histogram(Ctx *c, Hist *out);
 void sparse_free(Ctx *c);
 
 double now_ms();

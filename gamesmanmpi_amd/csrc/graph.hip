@@ -13,6 +13,7 @@
 // Rounds = the height of the graph; a position is written once, when final, so
 // reading a child in the round it is written is benign.
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 #include <algorithm>
 
@@ -77,6 +78,15 @@ __global__ void graph_digest_kernel(const uint16_t *__restrict__ score, uint64_t
         sum += digest_term(i, record_of_score(score[i]));
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     if ((threadIdx.x & 63) == 0) atomicAdd(acc, (unsigned long long)sum);
+}
+
+// census of the nodes' scores (hist_common.hpp score bins: LDS, or global for deep graphs)
+__global__ void graph_hist_kernel(const uint16_t *__restrict__ score, uint64_t n, unsigned long long *bins,
+                                  uint32_t nbin, int use_lds) {
+    uint32_t *lds = score_bins_open(nbin, use_lds);
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        score_bin_add(lds, bins, nbin, score[i], 1u);
+    score_bins_flush(lds, bins, nbin);
 }
 
 static unsigned grid_of(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
@@ -185,6 +195,23 @@ int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     GM_HIP(hipStreamSynchronize(c->stream));
     *digest = h;
     *n = g->n;
+    return GM_OK;
+}
+
+// Remoteness is below the node count (a round may resolve several levels, so the rounds do not
+// bound it): first the bins that fit in LDS, and for a graph deeper than those the global bins
+int graph_histogram(Ctx *c, Hist *out) {
+    Graph *g = c->graph;
+    const uint32_t full = (uint32_t)std::min<uint64_t>(g->n, MAX_REMOTENESS + 1), lds = HIST_LDS_BUDGET / 12;
+    for (uint32_t nbin : {std::min(full, lds), full}) {
+        ScoreBins b;
+        GM_TRY(score_bins_begin(c, nbin, &b));
+        hipLaunchKernelGGL(graph_hist_kernel, dim3(std::min(grid_of(g->n), 2048u)), dim3(256), b.lds_bytes, c->stream,
+                           g->score, g->n, b.d, b.nbin, b.use_lds);
+        bool deeper = false;
+        GM_TRY(score_bins_end(c, &b, out, nbin < full ? &deeper : nullptr));
+        if (!deeper) break;
+    }
     return GM_OK;
 }
 

@@ -7,6 +7,7 @@
 // deepest (Process.resolve, :223-265), both over LDS arrays, with one barrier
 // per tier.  A launch-bound config: the table is 58 KB, far below any roofline.
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 namespace gm {
 
@@ -136,6 +137,13 @@ int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
         if (s->h_rec[i] != REC_UNSOLVED) { d += digest_term(i, s->h_rec[i]); k++; }
     *digest = d;
     *n = k;
+    return GM_OK;
+}
+
+int small_dense_histogram(Ctx *c, Hist *out) {
+    SmallDense *s = c->sd;
+    for (uint32_t i = 0; i < s->slots; i++)
+        if (s->h_rec[i] != REC_UNSOLVED) out->add(s->h_rec[i] >> 14, s->h_rec[i] & 0x3FFFu, 1);
     return GM_OK;
 }
 

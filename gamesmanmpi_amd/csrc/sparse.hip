@@ -931,6 +931,22 @@ int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     return GM_OK;
 }
 
+// remoteness is below the number of tiers walked: 3 x (tiers + 1) bins (hist_common.hpp)
+int sparse_histogram(Ctx *c, Hist *out) {
+    Sparse *sp = c->sp;
+    ScoreBins b;
+    GM_TRY(score_bins_begin(c, (uint32_t)sp->tiers.size() + 1, &b));
+    int rc = with_desc(c, [&](const auto &d) {
+        for (auto &T : sp->tiers)
+            if (T.count)
+                hipLaunchKernelGGL(res_hist_kernel<std::decay_t<decltype(d)>>, dim3(grid_counted(T.cap)), dim3(256),
+                                   b.lds_bytes, c->stream, d, T.slots, T.cap, b.d, b.nbin, b.use_lds);
+        return GM_OK;
+    });
+    const int rc2 = score_bins_end(c, &b, out);
+    return rc != GM_OK ? rc : rc2;
+}
+
 void sparse_free(Ctx *c) {
     Sparse *sp = c->sp;
     if (!sp) return;

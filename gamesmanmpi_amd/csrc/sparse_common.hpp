@@ -2,6 +2,7 @@
 // the tables themselves).
 #pragma once
 #include "gm_internal.hpp"
+#include "hist_common.hpp"
 
 #include <algorithm>
 

@@ -436,6 +436,23 @@ __global__ void res_digest_kernel(D d, const typename KT<key_t<D>>::Slot *__rest
     block_add(acc, sum);
 }
 
+// census of a tier table: every stored representative counts once per member of its orbit
+template <class D>
+__global__ void res_hist_kernel(D d, const typename KT<key_t<D>>::Slot *__restrict__ s, uint64_t cap,
+                                unsigned long long *bins, uint32_t nbin, int use_lds) {
+    using K = key_t<D>;
+    uint32_t *lds = score_bins_open(nbin, use_lds);
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cap;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const K key = slot_key(s[i]);
+        if (key_empty(key)) continue;
+        uint32_t w = 0;
+        d.orbit(key, [&](const K &) { w++; });
+        score_bin_add(lds, bins, nbin, (uint16_t)slot_score(s[i]), w);
+    }
+    score_bins_flush(lds, bins, nbin);
+}
+
 template <class D>
 __global__ void res_gather_kernel(D d, const typename KT<key_t<D>>::Slot *__restrict__ s, uint64_t cap,
                                   key_t<D> *okeys, uint16_t *orec, unsigned long long *cursor) {

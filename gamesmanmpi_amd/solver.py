@@ -122,6 +122,16 @@ class Context:
         _lib.check(self.L.gm_digest(self.h, ctypes.byref(d), ctypes.byref(n)))
         return d.value, n.value
 
+    def histogram(self):
+        """gm_histogram: this rank's positions by value and remoteness, a (3, n_rem) uint64
+        array with rows WIN, LOSS, TIE (gamesmanmpi_amd/analysis.py)."""
+        n_rem, n = ctypes.c_int(), ctypes.c_uint64()
+        _lib.check(self.L.gm_histogram(self.h, None, 0, ctypes.byref(n_rem), ctypes.byref(n)))
+        out = np.zeros((3, n_rem.value), dtype=np.uint64)
+        _lib.check(self.L.gm_histogram(self.h, out.ctypes.data if out.size else None, n_rem.value,
+                                       ctypes.byref(n_rem), ctypes.byref(n)))
+        return out
+
     def stats(self):
         s = _lib.Stats()
         _lib.check(self.L.gm_stats(self.h, ctypes.byref(s)))
@@ -236,6 +246,17 @@ class Solver:
     def table(self):
         """Sorted keys and u16 records of every solved position."""
         return self.ctx.export()
+
+    def analysis(self):
+        """Positions of the whole solve on this rank by value and remoteness: a (3, n_rem)
+        uint64 array, rows WIN, LOSS, TIE (gamesmanmpi_amd/analysis.py).  The nodes of a graph
+        solve with symmetry generators are orbit representatives, which the device counts
+        once each: those (host-enumerated, small) graphs are weighted here by orbit size."""
+        if self.codec.game_id == _lib.GAME_GRAPH and self.codec.gens:
+            from . import analysis
+            keys, recs = self.ctx.export()
+            return analysis.from_records(recs, [len(self.codec.members(k)) for k in keys])
+        return self.ctx.histogram()
 
     def close(self):
         self.ctx.close()

@@ -298,6 +298,25 @@ int gm_query(gm_ctx *ctx, const uint64_t *keys, uint16_t *records, uint64_t n);
  * computed on the device; sums of the ranks' digests compare across world sizes. */
 int gm_digest(gm_ctx *ctx, uint64_t *digest, uint64_t *n);
 
+/* Census of this rank's solved table by value and remoteness, counted on the device in one
+ * streaming pass over the table (no export, no host sort).
+ * counts[v * cap + r] = positions with value v (0 WIN, 1 LOSS, 2 TIE, the codes of
+ * src/utils.py:4) and remoteness r.
+ * *n_rem = 1 + the largest remoteness this rank holds (0 if it holds none).
+ * *n = positions counted: exactly the positions gm_digest counts for this context (the root's
+ * region; every member of a stored representative's symmetry orbit; all virtual ranks; in a
+ * multi-process solve the keys this rank holds, so the ranks' arrays add up to the one-GPU
+ * answer).  One-word and multi-word key contexts alike.
+ * counts == NULL: only *n_rem and *n are set (the census is kept for the fill call that
+ * follows, so a query and its fill read the table once).
+ * cap < *n_rem: GM_E_CAP, with *n_rem and *n still set.
+ * Columns r in [*n_rem, cap) are zeroed.
+ * Before a solve: GM_E_STATE.
+ * Replaces reading the `resolved` / `remote` shelves back and tallying them on the host
+ * (src/cache_dict.py:38-79), the only route to such statistics in the reference, whose
+ * -sd/--statsdir stores the raw tables only (src/new_process.py:76-78). */
+int gm_histogram(gm_ctx *ctx, uint64_t *counts, int cap, int *n_rem, uint64_t *n);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

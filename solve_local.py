@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
-    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness]
+    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -9,7 +9,8 @@ process and prints "Winning position", "Losing position", "Tie" or "Draw"
 are strings while plugins return src.utils ints (:6), and its TIE
 branch tests LOSS twice (:34).  This drop-in prints the message the reference
 intends for the root's canonical value, computed on the GPU by libgmsolve.so;
-``--remoteness`` adds the launcher's "<V> in <R> moves" line.
+``--remoteness`` adds the launcher's "<V> in <R> moves" line, ``--analysis`` the table of
+positions by value and remoteness (gamesmanmpi_amd/analysis.py).
 """
 import argparse
 import os
@@ -32,6 +33,7 @@ def main(argv=None):
     p.add_argument("--dims")
     p.add_argument("--heaps", type=int)
     p.add_argument("--remoteness", action="store_true")
+    p.add_argument("--analysis", action="store_true")
     p.add_argument("--device", type=int, default=-1)
     args = p.parse_args(argv)
     args.engine = "auto"
@@ -42,6 +44,9 @@ def main(argv=None):
     print(MESSAGES[s.value])
     if args.remoteness:
         print(s.root_line())
+    if args.analysis:
+        from gamesmanmpi_amd import analysis
+        print(analysis.format_table(s.analysis()))
     s.close()
     return 0
 

@@ -28,7 +28,10 @@ Differences, on purpose:
   u64 keys + u16 records); ``--sd-format`` picks one (shelves are written for
   tables of up to 2 million positions unless asked for explicitly);
 * extras: ``--dims LxH`` patches board plugins' ``length``/``height``, ``--heaps``
-  patches the subtraction plugin, ``--engine``, ``--device``, ``--stats``.
+  patches the subtraction plugin, ``--engine``, ``--device``, ``--stats``;
+* ``--analysis`` prints, after the root line, the whole solve's positions by value and
+  remoteness (gm_histogram, gamesmanmpi_amd/analysis.py); with ``-sd DIR`` rank 0 also
+  writes them to ``DIR/stats/analysis.json``.
 """
 import argparse
 import cProfile
@@ -62,6 +65,8 @@ def build_parser():
     p.add_argument("--engine", choices=("auto", "dense", "sparse"), default="auto")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--stats", action="store_true", help="print solve statistics (JSON) to stderr")
+    p.add_argument("--analysis", action="store_true",
+                   help="after the root line, print the positions by value and remoteness")
     p.add_argument("--sd-format", choices=("auto", "npz", "reference", "both"), default="auto",
                    help="-sd output: npz table, the reference's shelve layout, or both (auto: both up to "
                         "%d positions, else npz)" % SHELVE_AUTO_LIMIT)
@@ -195,6 +200,8 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     if rank == 0:
         out.write(solver.root_line() + "\n")
         out.flush()
+    if getattr(args, "analysis", False):
+        report_analysis(args, solver, rank, world, plan, out)
     if args.stats:
         st = solver.ctx.stats()
         st["rank"] = rank
@@ -205,6 +212,31 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     if plan == "single":
         dist.release_waiters(world)
     return 0
+
+
+def report_analysis(args, solver, rank, world, plan, out):
+    """--analysis: the whole solve's histogram, printed by rank 0 (and written to
+    DIR/stats/analysis.json with -sd DIR).  Sharded ranks each count their own keys and the
+    arrays, padded to a common depth, are summed over the process group; a solo or single
+    solve's context already holds every position."""
+    from gamesmanmpi_amd import analysis
+    hist = solver.analysis()
+    if plan == "sharded" and world > 1:
+        import torch.distributed as tdist
+        parts = [None] * world
+        tdist.all_gather_object(parts, hist)
+        depth = max(p.shape[1] for p in parts)
+        hist = sum(analysis.pad(p, depth) for p in parts)
+    if rank != 0:
+        return
+    out.write(analysis.format_table(hist) + "\n")
+    out.flush()
+    if args.statsdir:
+        path = os.path.join(args.statsdir, "stats", "analysis.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(analysis.as_json(hist), f, indent=1)
+            f.write("\n")
 
 
 def write_statsdir(args, solver, rank, world, gather=True):
