@@ -599,16 +599,19 @@ int gm_query_key(gm_ctx *h, const uint64_t *words, uint16_t *recs, uint64_t n) {
 
 int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid,
                    uint16_t *root_record) {
-    if (!h || !prim || !off || (off[n] && !kid)) return GM_E_ARG;
+    if (!h) return GM_E_ARG;
     Ctx *c = &h->c;
     if (c->game != GM_GAME_GRAPH) { set_error("gm_solve_graph needs a GM_GAME_GRAPH context"); return GM_E_GAME; }
+    // from here on a failure leaves the context without a table: the one it held is not this graph's
+    c->solved = false;
+    c->hist_is_kept = false;
+    if (!prim || !off) { set_error("gm_solve_graph needs primitive and child_off"); return GM_E_ARG; }
     if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
     if (n >= (1ull << 32)) { set_error("graphs are limited to 2^32 - 1 positions"); return GM_E_ARG; }
     for (uint64_t i = 0; i < n; i++)
         if (off[i + 1] < off[i]) { set_error("child_off is not monotone at %llu", (unsigned long long)i); return GM_E_ARG; }
+    if (off[n] && !kid) { set_error("gm_solve_graph needs child_idx"); return GM_E_ARG; }
     GM_HIP(hipSetDevice(c->device));
-    c->solved = false;
-    c->hist_is_kept = false;
     c->stats = gm_stats_t{};
     c->stats.world = 1;
     GM_TRY(graph_solve(c, n, prim, off, kid));

@@ -199,10 +199,12 @@ int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 }
 
 // Remoteness is below the node count (a round may resolve several levels, so the rounds do not
-// bound it): first the bins that fit in LDS, and for a graph deeper than those the global bins
+// bound it) and at most 0x3FFF, which a chain ending in a LOSS or TIE leaf reaches (score_overflows
+// lets the last step through): first the bins that fit in LDS, and for a graph deeper than those the
+// global bins
 int graph_histogram(Ctx *c, Hist *out) {
     Graph *g = c->graph;
-    const uint32_t full = (uint32_t)std::min<uint64_t>(g->n, MAX_REMOTENESS + 1), lds = HIST_LDS_BUDGET / 12;
+    const uint32_t full = (uint32_t)std::min<uint64_t>(g->n, MAX_REMOTENESS + 2), lds = HIST_LDS_BUDGET / 12;
     for (uint32_t nbin : {std::min(full, lds), full}) {
         ScoreBins b;
         GM_TRY(score_bins_begin(c, nbin, &b));

@@ -276,6 +276,9 @@ int gm_query_key(gm_ctx *ctx, const uint64_t *key_words, uint16_t *records, uint
  * The device resolves every position (Appendix A); keys of gm_export / gm_query /
  * gm_digest are then the position indices.  A cycle, a DRAW primitive or an
  * undecided position without children is an error (the reference would hang).
+ * A remoteness up to 0x3FFE always solves and one past 0x3FFF is GM_E_CAP.  After
+ * any failed call the context holds no table (gm_export & co. return GM_E_STATE)
+ * until the next solve succeeds.
  * Replaces the reference's per-position job loop for arbitrary plugins
  * (src/new_process.py:37-265, GameState.expand src/game_state.py:33-41). */
 int gm_solve_graph(gm_ctx *ctx, uint64_t n, const uint8_t *primitive, const uint64_t *child_off,
