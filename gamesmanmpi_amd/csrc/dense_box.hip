@@ -1507,7 +1507,7 @@ static void box_region_tiers(uint32_t root_hi, std::vector<uint32_t> &boxes, std
     }
 }
 
-void dense_box_free(Ctx *c);
+static void dense_box_free(Ctx *c);
 
 // A half-built context is never kept: every failure path frees it.
 static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
@@ -1620,12 +1620,7 @@ void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc) {
     }
 }
 
-int dense_box_solve(Ctx *c, uint64_t root) {
-    if (c->world > 1 || c->virtual_ranks > 1) {   // the split solve (dist_box.hip)
-        dense_box_free(c);
-        return dist_box_solve(c, root);
-    }
-    dist_box_free(c);
+static int dense_box_solve(Ctx *c, uint64_t root) {
     DenseBox *d = c->dbox;
     const uint32_t rh = box_index_of_key((uint32_t)root) >> 12;
     if (!d || (c->adopted_dense && d->table != c->adopted_dense) || d->root_hi != rh || d->flow != box_flow_wanted(c)) {
@@ -1734,25 +1729,11 @@ int dense_box_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-int dense_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    if (c->dist_box) return dist_box_query(c, keys, recs, n);
+static int dense_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     DenseBox *d = c->dbox;
-    if (!n) return GM_OK;
-    uint64_t *dk;
-    uint16_t *dr;
-    const uint64_t chunk = std::min<uint64_t>(n, 1ull << 26);
-    GM_HIP(hipMalloc(&dk, chunk * 8));
-    GM_HIP(hipMalloc(&dr, chunk * 2));
-    for (uint64_t o = 0; o < n; o += chunk) {
-        const uint64_t m = std::min(chunk, n - o);
-        GM_HIP(hipMemcpyAsync(dk, keys + o, m * 8, hipMemcpyHostToDevice, c->stream));
+    return query_keys(c, keys, recs, n, BOX_QUERY_CHUNK, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
         box_launch_query(d->d_tables, nullptr, c->root, dk, dr, m, c->stream);
-        GM_HIP(hipMemcpyAsync(recs + o, dr, m * 2, hipMemcpyDeviceToHost, c->stream));
-    }
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    return GM_OK;
+    });
 }
 
 // keys of the root's region in ascending order (heap 0 fastest)
@@ -1771,8 +1752,7 @@ void box_region_keys(uint64_t root, uint64_t *keys, uint64_t n) {
 }
 
 // Export: the root's region in ascending key order.
-int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    if (c->dist_box) return dist_box_export(c, keys, recs, cap, n);
+static int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     DenseBox *d = c->dbox;
     *n = c->n_positions;
     if (!keys) return GM_OK;
@@ -1781,7 +1761,7 @@ int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint6
         return GM_E_CAP;
     }
     box_region_keys(c->root, keys, c->n_positions);
-    if (c->n_positions <= (1ull << 26)) return dense_box_query(c, keys, recs, c->n_positions);
+    if (c->n_positions <= BOX_QUERY_CHUNK) return dense_box_query(c, keys, recs, c->n_positions);
     // large regions: one copy of the table, decoded on the host
     std::vector<uint8_t> tab(1ull << 32);
     GM_HIP(hipMemcpy(tab.data(), d->table, tab.size(), hipMemcpyDeviceToHost));
@@ -1789,8 +1769,7 @@ int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint6
     return GM_OK;
 }
 
-int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    if (c->dist_box) return dist_box_digest(c, digest, n);
+static int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     DenseBox *d = c->dbox;
     GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
     box_launch_digest(d->table, d->d_boxes, d->boxes.size(), c->root, (unsigned long long *)d->d_acc, c->stream);
@@ -1804,8 +1783,7 @@ int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 }
 
 // census of the region's boxes (hist_common.hpp)
-int dense_box_histogram(Ctx *c, Hist *out) {
-    if (c->dist_box) return dist_box_histogram(c, out);
+static int dense_box_histogram(Ctx *c, Hist *out) {
     DenseBox *d = c->dbox;
     CodeBins b;
     GM_TRY(code_bins_begin(c, &b));
@@ -1814,14 +1792,13 @@ int dense_box_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
-int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
-    if (c->dist_box) return dist_box_table(c, p, bytes);
+static int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
     *p = c->dbox->table;
     *bytes = 1ull << 32;
     return GM_OK;
 }
 
-void dense_box_free(Ctx *c) {
+static void dense_box_free(Ctx *c) {
     DenseBox *d = c->dbox;
     if (!d) return;
     if (d->graph) (void)hipGraphExecDestroy(d->graph);
@@ -1834,5 +1811,8 @@ void dense_box_free(Ctx *c) {
     delete d;
     c->dbox = nullptr;
 }
+
+GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
+                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_table, dense_box_free)
 
 }  // namespace gm

@@ -1068,15 +1068,9 @@ static int launch_tiers(Ctx *c, DenseSub *d, bool timed) {
     return GM_OK;
 }
 
-int dense_sub_solve(Ctx *c, uint64_t root) {
-    if (c->sub.heaps == 8 && c->sub_interleave == 20) {   // the box engine (dense_box.hip)
-        dense_sub_free(c);
-        c->dbox_active = true;
-        return dense_box_solve(c, root);
-    }
-    dense_box_free(c);
-    dist_box_free(c);
-    c->dbox_active = false;
+static void dense_sub_free(Ctx *c);
+
+static int dense_sub_solve(Ctx *c, uint64_t root) {
     DenseSub *d = c->dsub;
     if (!d || d->heaps != c->sub.heaps || d->want_threads != c->sub_threads || d->want_x4 != c->sub_interleave ||
         d->want_order != c->sub_order || d->low != std::min(std::max(c->sub_low, 1), std::min(3, c->sub.heaps)) ||
@@ -1183,8 +1177,7 @@ int dense_sub_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    if (c->dbox_active) return dense_box_export(c, keys, recs, cap, n);
+static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     DenseSub *d = c->dsub;
     *n = c->n_positions;
     if (!keys) return GM_OK;
@@ -1206,26 +1199,15 @@ int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint6
     return GM_OK;
 }
 
-int dense_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    if (c->dbox_active) return dense_box_query(c, keys, recs, n);
+static int dense_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     DenseSub *d = c->dsub;
-    if (!n) return GM_OK;
-    uint64_t *dk;
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&dk, n * 8));
-    GM_HIP(hipMalloc(&dr, n * 2));
-    GM_HIP(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sub_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d->table,
-                       d->slots, c->root, c->sub.heaps, dk, dr, n);
-    GM_HIP(hipMemcpyAsync(recs, dr, n * 2, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    return GM_OK;
+    return query_keys(c, keys, recs, n, n, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
+        hipLaunchKernelGGL(sub_query_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, d->table,
+                           d->slots, c->root, c->sub.heaps, dk, dr, m);
+    });
 }
 
-int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    if (c->dbox_active) return dense_box_digest(c, digest, n);
+static int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     DenseSub *d = c->dsub;
     GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
     hipLaunchKernelGGL(sub_digest_kernel, dim3(2048), dim3(256), 0, c->stream, d->table, d->slots, d->heaps, c->root,
@@ -1239,8 +1221,7 @@ int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 }
 
 // census of the root's region: the table is one unit of 16^heaps bytes, slot = key
-int dense_sub_histogram(Ctx *c, Hist *out) {
-    if (c->dbox_active) return dense_box_histogram(c, out);
+static int dense_sub_histogram(Ctx *c, Hist *out) {
     DenseSub *d = c->dsub;
     CodeBins b;
     GM_TRY(code_bins_begin(c, &b));
@@ -1249,15 +1230,14 @@ int dense_sub_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
-int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {
-    if (c->dbox_active) return dense_box_table(c, p, bytes);
+static int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {
     DenseSub *d = c->dsub;
     *p = d->table;
     *bytes = d->slots;
     return GM_OK;
 }
 
-void dense_sub_free(Ctx *c) {
+static void dense_sub_free(Ctx *c) {
     DenseSub *d = c->dsub;
     if (!d) return;
     if (d->graph) (void)hipGraphExecDestroy(d->graph);
@@ -1269,5 +1249,8 @@ void dense_sub_free(Ctx *c) {
     delete d;
     c->dsub = nullptr;
 }
+
+GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
+                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_table, dense_sub_free)
 
 }  // namespace gm

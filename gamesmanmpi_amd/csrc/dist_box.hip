@@ -777,7 +777,7 @@ static int bx_upload(const std::vector<uint32_t> &v, uint32_t **d) {
     return GM_OK;
 }
 
-void dist_box_free(Ctx *c);
+static void dist_box_free(Ctx *c);
 
 static int bx_prepare(Ctx *c, DistBox *d, uint64_t root, int G, bool loopback) {
     d->loopback = loopback;
@@ -1283,7 +1283,7 @@ static int bx_launch(Ctx *c, DistBox *d, bool op_events) {
     return GM_OK;
 }
 
-int dist_box_solve(Ctx *c, uint64_t root) {
+static int dist_box_solve(Ctx *c, uint64_t root) {
     const bool loopback = c->world <= 1 && c->virtual_ranks > 1;
     const int G = loopback ? c->virtual_ranks : c->world;
     const bool ipc = !loopback && c->box_transport == 1;
@@ -1425,29 +1425,16 @@ int dist_box_solve(Ctx *c, uint64_t root) {
 }
 
 // ---------------------------------------------------------------------------- results
-int dist_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int dist_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     DistBox *d = c->dist_box;
-    if (!n) return GM_OK;
-    uint64_t *dk;
-    uint16_t *dr;
-    const uint64_t chunk = std::min<uint64_t>(n, 1ull << 26);
-    GM_HIP(hipMalloc(&dk, chunk * 8));
-    GM_HIP(hipMalloc(&dr, chunk * 2));
-    for (uint64_t o = 0; o < n; o += chunk) {
-        const uint64_t m = std::min(chunk, n - o);
-        GM_HIP(hipMemcpyAsync(dk, keys + o, m * 8, hipMemcpyHostToDevice, c->stream));
+    return query_keys(c, keys, recs, n, BOX_QUERY_CHUNK, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
         box_launch_query(d->d_tables, d->d_owner, c->root, dk, dr, m, c->stream);
-        GM_HIP(hipMemcpyAsync(recs + o, dr, m * 2, hipMemcpyDeviceToHost, c->stream));
-    }
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    return GM_OK;
+    });
 }
 
 // Export: every virtual rank together = the root's region; a rank of a multi-process solve:
 // the positions of the boxes it computed, ascending.
-int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     DistBox *d = c->dist_box;
     if (d->loopback) {
         *n = c->n_positions;
@@ -1480,7 +1467,7 @@ int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64
 
 // Digest of the boxes this context's ranks computed: the whole region over all virtual ranks,
 // this rank's part in a multi-process solve (the parts sum to the whole).
-int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+static int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     DistBox *d = c->dist_box;
     GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
     for (auto &R : d->ranks)
@@ -1495,7 +1482,7 @@ int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 }
 
 // census of the same boxes: every virtual rank's, or this process's own
-int dist_box_histogram(Ctx *c, Hist *out) {
+static int dist_box_histogram(Ctx *c, Hist *out) {
     DistBox *d = c->dist_box;
     CodeBins b;
     GM_TRY(code_bins_begin(c, &b));
@@ -1506,7 +1493,7 @@ int dist_box_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
-int dist_box_table(Ctx *c, void **p, uint64_t *bytes) {
+static int dist_box_table(Ctx *c, void **p, uint64_t *bytes) {
     DistBox *d = c->dist_box;
     *p = d->ranks[0].table;
     *bytes = d->ranks[0].table ? 1ull << 32 : 0;
@@ -1539,7 +1526,7 @@ int dist_box_op_ms(Ctx *c, int rank, double *ms, int cap, int *n) {
     return GM_OK;
 }
 
-void dist_box_free(Ctx *c) {
+static void dist_box_free(Ctx *c) {
     DistBox *d = c->dist_box;
     if (!d) return;
     (void)hipDeviceSynchronize();
@@ -1668,5 +1655,8 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
     std::copy(v.begin(), v.end(), out);
     return GM_OK;
 }
+
+GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
+                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_table, dist_box_free)
 
 }  // namespace gm

@@ -909,6 +909,8 @@ static int self_expand(Ctx *c, DistSparseK<key_t<D>> *d, const D &desc, size_t t
     return GM_OK;
 }
 
+static void dist_sparse_free(Ctx *c);
+
 template <class D>
 static int solve_sharded(Ctx *c, const D &desc, const key_t<D> &root) {
     using K = key_t<D>;
@@ -1246,25 +1248,6 @@ static int solve_sharded(Ctx *c, const D &desc, const key_t<D> &root) {
     return GM_OK;
 }
 
-// the context's descriptor: the 64-bit-key games (with_game) or Othello 8x8 (K128 keys)
-template <class F>
-static int with_game(Ctx *c, F &&f) {
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: return f(c->f2o);
-    case GM_GAME_TTT: return f(c->ttt);
-    case GM_GAME_TOOT: return f(c->toot);
-    case GM_GAME_OTHELLO: return f(c->oth);
-    case GM_GAME_SUBTRACT: return f(c->sub);
-    }
-    set_error("unknown game");
-    return GM_E_GAME;
-}
-template <class F>
-static int with_any_game(Ctx *c, F &&f) {
-    if (c->wide) return f(c->oth8);
-    return with_game(c, f);
-}
-
 static int finish_solve(Ctx *c, int rc) {
     // IPC: a rank that leaves with an error marks the segment, so its peers' next barrier fails
     // at once instead of waiting out the limit
@@ -1272,9 +1255,9 @@ static int finish_solve(Ctx *c, int rc) {
     return rc;
 }
 
-int dist_sparse_solve(Ctx *c, uint64_t root) {
+static int dist_sparse_solve(Ctx *c, uint64_t root) {
     if (c->wide) { set_error("this game's keys are 128-bit: gm_solve_key"); return GM_E_ARG; }
-    return finish_solve(c, with_game(c, [&](const auto &desc) { return solve_sharded(c, desc, root); }));
+    return finish_solve(c, with_desc(c, [&](const auto &desc) { return solve_sharded(c, desc, root); }));
 }
 
 int dist_sparse_solve_wide(Ctx *c, const K128 &root) {
@@ -1282,47 +1265,25 @@ int dist_sparse_solve_wide(Ctx *c, const K128 &root) {
     return finish_solve(c, solve_sharded(c, c->oth8, root));
 }
 
-// every rank's positions (each representative's orbit expanded), sorted by key
-template <class D>
-static int export_ranks(Ctx *c, const D &desc, key_t<D> *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    using K = key_t<D>;
-    auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
-    uint64_t total = 0;
-    for (auto &R : d->ranks)
-        for (auto &T : R.tiers) total += T.count_all;
-    *n = total;
-    if (!keys) return GM_OK;
-    if (cap < total) { set_error("export buffer too small"); return GM_E_CAP; }
-    K *dk;
-    uint16_t *dr;
-    unsigned long long *cur;
-    GM_HIP(hipMalloc(&dk, std::max<uint64_t>(1, total) * sizeof(K)));
-    GM_HIP(hipMalloc(&dr, std::max<uint64_t>(1, total) * 2));
-    GM_HIP(hipMalloc(&cur, 8));
-    GM_HIP(hipMemsetAsync(cur, 0, 8, c->stream));
-    for (auto &R : d->ranks)
-        for (auto &T : R.tiers)
-            if (T.count)
-                hipLaunchKernelGGL(res_gather_kernel<D>, dim3(grid_for(T.cap)), dim3(256), 0, c->stream, desc, T.slots,
-                                   T.cap, dk, dr, cur);
-    std::vector<K> hk(total);
-    std::vector<uint16_t> hr(total);
-    GM_HIP(hipMemcpyAsync(hk.data(), dk, total * sizeof(K), hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipMemcpyAsync(hr.data(), dr, total * 2, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    (void)hipFree(cur);
-    std::vector<uint64_t> idx(total);
-    for (uint64_t i = 0; i < total; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return hk[a] < hk[b]; });
-    for (uint64_t i = 0; i < total; i++) { keys[i] = hk[idx[i]]; recs[i] = hr[idx[i]]; }
-    return GM_OK;
+// the tier tables of every rank this context runs (its hash share in a multi-process solve)
+template <class K>
+static TierList<K> rank_tiers(Ctx *c) {
+    TierList<K> l;
+    for (auto &R : static_cast<DistSparseK<K> *>(c->dist_sp)->ranks)
+        for (auto &T : R.tiers) l.push_back(&T);
+    return l;
 }
 
-int dist_sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+template <class D>
+static int export_ranks(Ctx *c, const D &desc, key_t<D> *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    const int rc = tiers_export(c, desc, rank_tiers<key_t<D>>(c), keys, recs, cap, n);
+    if (rc == GM_E_CAP) set_error("export buffer too small");
+    return rc;
+}
+
+static int dist_sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     if (c->wide) { set_error("this game's keys are 128-bit: gm_export_key"); return GM_E_ARG; }
-    return with_game(c, [&](const auto &desc) { return export_ranks(c, desc, keys, recs, cap, n); });
+    return with_desc(c, [&](const auto &desc) { return export_ranks(c, desc, keys, recs, cap, n); });
 }
 
 int dist_sparse_export_wide(Ctx *c, K128 *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
@@ -1330,90 +1291,35 @@ int dist_sparse_export_wide(Ctx *c, K128 *keys, uint16_t *recs, uint64_t cap, ui
     return export_ranks(c, c->oth8, keys, recs, cap, n);
 }
 
-int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    unsigned long long *acc;
-    GM_HIP(hipMalloc(&acc, 8));
-    GM_HIP(hipMemsetAsync(acc, 0, 8, c->stream));
-    uint64_t total = 0;
-    GM_TRY(with_any_game(c, [&](const auto &desc) {
-        using D = std::decay_t<decltype(desc)>;
-        auto *d = static_cast<DistSparseK<key_t<D>> *>(c->dist_sp);
-        for (auto &R : d->ranks)
-            for (auto &T : R.tiers) {
-                total += T.count_all;
-                if (T.count)
-                    hipLaunchKernelGGL(res_digest_kernel<D>, dim3(grid_counted(T.cap)), dim3(256), 0, c->stream, desc,
-                                       T.slots, T.cap, acc);
-            }
-        return GM_OK;
-    }));
-    unsigned long long h;
-    GM_HIP(hipMemcpyAsync(&h, acc, 8, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(acc);
-    *digest = h;
-    *n = total;
-    return GM_OK;
-}
-
-// census of the tier tables of this context's ranks (its hash share in a multi-process solve)
-int dist_sparse_histogram(Ctx *c, Hist *out) {
-    ScoreBins b;
-    bool begun = false;
-    int rc = with_any_game(c, [&](const auto &desc) -> int {
-        using D = std::decay_t<decltype(desc)>;
-        auto *d = static_cast<DistSparseK<key_t<D>> *>(c->dist_sp);
-        size_t tiers = 0;
-        for (auto &R : d->ranks) tiers = std::max(tiers, R.tiers.size());
-        GM_TRY(score_bins_begin(c, (uint32_t)tiers + 1, &b));
-        begun = true;
-        for (auto &R : d->ranks)
-            for (auto &T : R.tiers)
-                if (T.count)
-                    hipLaunchKernelGGL(res_hist_kernel<D>, dim3(grid_counted(T.cap)), dim3(256), b.lds_bytes, c->stream,
-                                       desc, T.slots, T.cap, b.d, b.nbin, b.use_lds);
-        return GM_OK;
+static int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        return tiers_digest(c, desc, rank_tiers<key_t<std::decay_t<decltype(desc)>>>(c), digest, n);
     });
-    if (!begun) return rc;
-    const int rc2 = score_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
 }
 
+static int dist_sparse_histogram(Ctx *c, Hist *out) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        using K = key_t<std::decay_t<decltype(desc)>>;
+        size_t depth = 0;
+        for (auto &R : static_cast<DistSparseK<K> *>(c->dist_sp)->ranks) depth = std::max(depth, R.tiers.size());
+        return tiers_histogram(c, desc, rank_tiers<K>(c), depth, out);
+    });
+}
+
+// a key is stored by its owner rank: one group of tables per rank
 template <class D>
 static int query_ranks(Ctx *c, const D &desc, const key_t<D> *keys, uint16_t *recs, uint64_t n) {
     using K = key_t<D>;
-    using Res = typename KT<K>::Res;
     auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
-    K *dk;
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&dk, n * sizeof(K)));
-    GM_HIP(hipMalloc(&dr, n * 2));
-    GM_HIP(hipMemcpyAsync(dk, keys, n * sizeof(K), hipMemcpyHostToDevice, c->stream));
-    std::vector<uint16_t> part(n);
-    for (uint64_t i = 0; i < n; i++) recs[i] = REC_UNSOLVED;
-    for (auto &R : d->ranks) {
-        std::vector<Res> h(R.tiers.size());
-        for (size_t t = 0; t < h.size(); t++) h[t] = res_ref_of(R.tiers[t]);
-        Res *tabs;
-        GM_HIP(hipMalloc(&tabs, std::max<size_t>(1, h.size()) * sizeof(Res)));
-        if (!h.empty()) GM_HIP(hipMemcpyAsync(tabs, h.data(), h.size() * sizeof(Res), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(query_kernel<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, desc,
-                           d->t_root, tabs, (int)h.size(), dk, dr, n);
-        GM_HIP(hipMemcpyAsync(part.data(), dr, n * 2, hipMemcpyDeviceToHost, c->stream));
-        GM_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(tabs);
-        for (uint64_t i = 0; i < n; i++)
-            if (part[i] != REC_UNSOLVED) recs[i] = part[i];
-    }
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    return GM_OK;
+    std::vector<TierGroup<K>> groups;
+    for (auto &R : d->ranks) groups.push_back({&R.tiers, d->t_root});
+    return tiers_query(c, desc, groups, keys, recs, n);
 }
 
-int dist_sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int dist_sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     if (!n) return GM_OK;
     if (c->wide) { set_error("this game's keys are 128-bit: gm_query_key"); return GM_E_ARG; }
-    return with_game(c, [&](const auto &desc) { return query_ranks(c, desc, keys, recs, n); });
+    return with_desc(c, [&](const auto &desc) { return query_ranks(c, desc, keys, recs, n); });
 }
 
 int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n) {
@@ -1439,7 +1345,7 @@ static void free_ranks(Ctx *c, DistSparseK<K> *d) {
     }
 }
 
-void dist_sparse_free(Ctx *c) {
+static void dist_sparse_free(Ctx *c) {
     DistSparse *d = c->dist_sp;
     if (!d) return;
     if (d->wide) free_ranks(c, static_cast<DistSparseK<K128> *>(d));
@@ -1453,5 +1359,8 @@ void dist_sparse_free(Ctx *c) {
     delete d;
     c->dist_sp = nullptr;
 }
+
+GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
+                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, nullptr, dist_sparse_free)
 
 }  // namespace gm

@@ -671,7 +671,9 @@ static int run_solve(Ctx *c, DistSub *d) {
     return GM_OK;
 }
 
-int dist_sub_solve(Ctx *c, uint64_t root) {
+static void dist_sub_free(Ctx *c);
+
+static int dist_sub_solve(Ctx *c, uint64_t root) {
     const bool loopback = c->virtual_ranks > 1;
     const int G = loopback ? c->virtual_ranks : c->world;
     DistSub *d = c->dist_sub;
@@ -736,7 +738,7 @@ static bool in_box(uint64_t k, uint64_t root, int heaps) {
     return true;
 }
 
-int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+static int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     DistSub *d = c->dist_sub;
     hipStream_t H = c->stream;
     GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, H));
@@ -754,7 +756,7 @@ int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 }
 
 // census of the blocks the ranks own: a block is 16^low contiguous bytes of its rank's table
-int dist_sub_histogram(Ctx *c, Hist *out) {
+static int dist_sub_histogram(Ctx *c, Hist *out) {
     DistSub *d = c->dist_sub;
     CodeBins b;
     GM_TRY(code_bins_begin(c, &b));
@@ -767,7 +769,7 @@ int dist_sub_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
-int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     DistSub *d = c->dist_sub;
     hipStream_t H = c->stream;
     const uint64_t bsz = 1ull << (4 * d->low);
@@ -776,15 +778,14 @@ int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64
     for (auto &R : d->ranks) {
         uint32_t nb = R.off.back();
         if (!nb) continue;
-        uint8_t *stg;
-        GM_HIP(hipMalloc(&stg, (uint64_t)nb * bsz));
+        DevBuf<uint8_t> stg;
+        GM_TRY(stg.alloc((uint64_t)nb * bsz));
         copy_blocks(d, R.table, R.dlist, nb, stg, true, H);
         std::vector<uint8_t> hs((uint64_t)nb * bsz);
         std::vector<uint32_t> hl(nb);
         GM_HIP(hipMemcpyAsync(hs.data(), stg, hs.size(), hipMemcpyDeviceToHost, H));
         GM_HIP(hipMemcpyAsync(hl.data(), R.dlist, nb * 4, hipMemcpyDeviceToHost, H));
         GM_HIP(hipStreamSynchronize(H));
-        (void)hipFree(stg);
         for (uint32_t b = 0; b < nb; b++)
             for (uint64_t i = 0; i < bsz; i++) {
                 uint64_t key = ((uint64_t)hl[b] << (4 * d->low)) + i;
@@ -801,7 +802,7 @@ int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64
     return GM_OK;
 }
 
-int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     DistSub *d = c->dist_sub;
     for (uint64_t i = 0; i < n; i++) {
         recs[i] = REC_UNSOLVED;
@@ -820,7 +821,7 @@ int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     return GM_OK;
 }
 
-void dist_sub_free(Ctx *c) {
+static void dist_sub_free(Ctx *c) {
     DistSub *d = c->dist_sub;
     if (!d) return;
     (void)hipDeviceSynchronize();
@@ -930,5 +931,8 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
     }
     return GM_OK;
 }
+
+GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
+                 dist_sub_query, dist_sub_digest, dist_sub_histogram, nullptr, dist_sub_free)
 
 }  // namespace gm

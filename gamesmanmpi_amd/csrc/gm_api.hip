@@ -106,35 +106,29 @@ void dev_free(Ctx *c, void *p) {
     (void)hipFree(p);   // not ours: plain free
 }
 
-static int engine_for(const Ctx *c) {
-    if (c->engine_opt == GM_ENGINE_SPARSE) return GM_ENGINE_SPARSE;
-    if (c->engine_opt == GM_ENGINE_DENSE) {
-        if (c->game == GM_GAME_SUBTRACT || c->game == GM_GAME_TTT) return GM_ENGINE_DENSE;
-        return GM_ENGINE_SPARSE;
-    }
-    return (c->game == GM_GAME_SUBTRACT || c->game == GM_GAME_TTT) ? GM_ENGINE_DENSE : GM_ENGINE_SPARSE;
+// The engine of a gm_solve, from the context's options: dense (SUBTRACT, tic-tac-toe) or sparse,
+// for the dense 8-heap game the box engine (GM_OPT_SUB_INTERLEAVE 20) or the block engine, and
+// one GPU or -- `sharded` -- split / partitioned / hash-sharded over ranks.  GM_ENGINE_DIST_SPARSE
+// forces the hash-sharded engine, e.g. over a one-rank communicator.
+static const Engine *choose_engine(const Ctx *c, bool sharded) {
+    const bool dense_game = c->game == GM_GAME_SUBTRACT || c->game == GM_GAME_TTT;
+    if (c->engine_opt == GM_ENGINE_DIST_SPARSE) return &dist_sparse_engine;
+    if (c->engine_opt == GM_ENGINE_SPARSE || !dense_game) return sharded ? &dist_sparse_engine : &sparse_engine;
+    if (c->game == GM_GAME_TTT) return sharded ? &dist_sparse_engine : &small_dense_engine;
+    // the 8-heap game on the box engine splits in dist_box.hip; other heap counts and
+    // GM_OPT_SUB_INTERLEAVE != 20 keep the block engine and its partitioned path
+    if (c->sub.heaps == 8 && c->sub_interleave == 20) return sharded ? &dist_box_engine : &dense_box_engine;
+    return sharded ? &dist_sub_engine : &dense_sub_engine;
 }
 
 static bool key_valid(const Ctx *c, uint64_t k) {
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: return c->f2o.valid(k);
-    case GM_GAME_TTT: return c->ttt.valid(k);
-    case GM_GAME_TOOT: return c->toot.valid(k);
-    case GM_GAME_OTHELLO: return c->oth.valid(k);
-    case GM_GAME_SUBTRACT: return c->sub.valid(k);
-    }
-    return false;
+    return with_desc(c, [&](const auto &d) { return (int)d.valid(k); }) > 0;
 }
 
 static void free_engines(Ctx *c) {
-    graph_free(c);
-    dense_sub_free(c);
-    dense_box_free(c);
-    small_dense_free(c);
-    sparse_free(c);
-    dist_sub_free(c);
-    dist_box_free(c);
-    dist_sparse_free(c);
+    for (const Engine *e : {&graph_engine, &dense_sub_engine, &dense_box_engine, &small_dense_engine, &sparse_engine,
+                            &dist_sub_engine, &dist_box_engine, &dist_sparse_engine})
+        e->free_(c);
 }
 
 }  // namespace gm
@@ -336,24 +330,13 @@ int gm_expand_host(gm_ctx *h, uint64_t key, uint64_t *children, int cap, int *n,
     int p = UNDECIDED, k = 0;
     int64_t t = 0;
     if (!key_valid(c, key)) { set_error("key is not a valid position"); return GM_E_KEY; }
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: p = c->f2o.primitive(key); t = c->f2o.tier(key); if (p == UNDECIDED) k = c->f2o.children(key, kids); break;
-    case GM_GAME_TTT: p = c->ttt.primitive(key); t = c->ttt.tier(key); if (p == UNDECIDED) k = c->ttt.children(key, kids); break;
-    case GM_GAME_TOOT: {   // the plugin's own moves: no symmetry reduction
-        DescToot d = c->toot;
-        d.sym = 0;
-        p = d.primitive(key); t = d.tier(key); if (p == UNDECIDED) k = d.children(key, kids);
-        break;
-    }
-    case GM_GAME_OTHELLO: {   // the plugin's own moves: no symmetry reduction
-        DescOthello d = c->oth;
-        d.sym = 0;
-        p = d.primitive(key); t = d.tier(key); if (p == UNDECIDED) k = d.children(key, kids);
-        break;
-    }
-    case GM_GAME_SUBTRACT: p = c->sub.primitive(key); t = c->sub.tier(key); if (p == UNDECIDED) k = c->sub.children(key, kids); break;
-    default: return GM_E_GAME;
-    }
+    GM_TRY(with_desc(c, [&](const auto &reduced) {
+        const auto d = unreduced(reduced);   // the plugin's own moves: no symmetry reduction (Toot, Othello)
+        p = d.primitive(key);
+        t = d.tier(key);
+        if (p == UNDECIDED) k = d.children(key, kids);
+        return GM_OK;
+    }));
     *prim = p;
     *tier = t;
     *n = k;
@@ -377,9 +360,7 @@ int gm_set_comm(gm_ctx *h, int rank, int world, const void *uid, int bytes) {
     // the sharded engines' transports (per-axis communicators split from c->comm, IPC
     // mappings) belong to the previous communicator: torn down first (dist_box_free
     // synchronises the device and destroys the split communicators), then the parent
-    if (c->dist_box) dist_box_free(c);
-    if (c->dist_sub) dist_sub_free(c);
-    if (c->dist_sp) dist_sparse_free(c);
+    for (const Engine *e : {&dist_box_engine, &dist_sub_engine, &dist_sparse_engine}) e->free_(c);
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
     c->rank = rank;
     c->world = world;
@@ -403,6 +384,7 @@ int gm_solve(gm_ctx *h, uint64_t root, uint64_t *n_positions, uint16_t *root_rec
     if (!key_valid(c, root)) { set_error("root key 0x%llx is not a valid position", (unsigned long long)root); return GM_E_KEY; }
     GM_HIP(hipSetDevice(c->device));
     c->solved = false;
+    c->solved_by = nullptr;
     c->hist_is_kept = false;
     int32_t launches = c->stats.kernel_launches;
     c->stats = gm_stats_t{};
@@ -413,49 +395,37 @@ int gm_solve(gm_ctx *h, uint64_t root, uint64_t *n_positions, uint16_t *root_rec
     if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(root) == root) ? 1u : 0u;
     // Othello: the board symmetries that fix the root (games.hpp DescOthello::sym)
     if (c->game == GM_GAME_OTHELLO) c->oth.sym = c->symmetry ? c->oth.stabilizer(root) : 0u;
-    int eng = engine_for(c);
-    // GM_ENGINE_DIST_SPARSE forces the hash-sharded engine, e.g. over a one-rank communicator
-    const bool force_dist_sparse = c->engine_opt == GM_ENGINE_DIST_SPARSE;
-    bool sharded = c->world > 1 || c->virtual_ranks > 1 || force_dist_sparse;
+    const bool sharded = c->world > 1 || c->virtual_ranks > 1 || c->engine_opt == GM_ENGINE_DIST_SPARSE;
     if (sharded && c->world > 1 && c->virtual_ranks > 1) {
         set_error("virtual ranks and a multi-process communicator are exclusive");
         return GM_E_ARG;
     }
-    // the 8-heap game on the box engine splits inside dense_box.hip (dist_box.hip); other
-    // heap counts and GM_OPT_SUB_INTERLEAVE != 20 keep the block engine's sharded path
-    const bool box = !force_dist_sparse && eng == GM_ENGINE_DENSE && c->game == GM_GAME_SUBTRACT &&
-                     c->sub.heaps == 8 && c->sub_interleave == 20;
+    const Engine *e = choose_engine(c, sharded);
     // transports that need no communicator: the split box engine's IPC stores and the sparse
     // engine's IPC pulls (both also run with the ranks sharing one GPU, where RCCL refuses)
-    const bool dense_sharded = !force_dist_sparse && eng == GM_ENGINE_DENSE && c->game == GM_GAME_SUBTRACT;
-    const bool no_comm = box ? c->box_transport == 1 : (!dense_sharded && c->sparse_transport == 1);
-    if (sharded && c->virtual_ranks <= 1 && (c->world > 1 || force_dist_sparse) && no_comm && !c->have_uid) {
+    const bool no_comm = e == &dist_box_engine ? c->box_transport == 1
+                                               : (e == &dist_sparse_engine && c->sparse_transport == 1);
+    if (sharded && c->virtual_ranks <= 1 && no_comm && !c->have_uid) {
         set_error("the IPC transport needs gm_set_comm with a unique id (it names the rendezvous)");
         return GM_E_COMM;
     }
-    if (sharded && c->virtual_ranks <= 1 && (c->world > 1 || force_dist_sparse) && !no_comm) {
+    if (sharded && c->virtual_ranks <= 1 && !no_comm) {
         if (!c->have_uid) {
             set_error("a %d-rank solve of this game needs an RCCL communicator (gm_set_comm with a unique id)", c->world);
             return GM_E_COMM;
         }
         GM_TRY(ensure_comm(c));
     }
-    if (sharded && !box) eng = dense_sharded ? GM_ENGINE_DIST_DENSE : GM_ENGINE_DIST_SPARSE;
-    int rc;
-    switch (eng) {
-    case GM_ENGINE_DENSE:
-        rc = c->game == GM_GAME_SUBTRACT ? dense_sub_solve(c, root) : small_dense_solve(c, root);
-        break;
-    case GM_ENGINE_DIST_DENSE: rc = dist_sub_solve(c, root); break;
-    case GM_ENGINE_DIST_SPARSE: rc = dist_sparse_solve(c, root); break;
-    default: rc = sparse_solve(c, root);
-    }
-    if (rc != GM_OK) return rc;
+    // each dense SUBTRACT engine holds (or adopts) a whole table: choosing one releases the other two's
+    if (e == &dense_box_engine || e == &dist_box_engine || e == &dense_sub_engine)
+        for (const Engine *o : {&dense_sub_engine, &dense_box_engine, &dist_box_engine})
+            if (o != e) o->free_(c);
+    GM_TRY(e->solve(c, root));
     if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;   // engines without a symmetry reduction
-    c->engine = eng;
-    c->stats.engine = (box && sharded) ? GM_ENGINE_DIST_DENSE : eng;
+    c->stats.engine = e->id;
     c->stats.world = sharded ? (c->world > 1 ? c->world : c->virtual_ranks) : 1;
     c->solved = true;
+    c->solved_by = e;
     if (n_positions) *n_positions = c->n_positions;
     if (root_record) *root_record = c->root_record;
     return GM_OK;
@@ -525,6 +495,7 @@ int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16
     }
     GM_HIP(hipSetDevice(c->device));
     c->solved = false;
+    c->solved_by = nullptr;
     c->hist_is_kept = false;
     c->stats = gm_stats_t{};
     if (c->world > 1 && c->virtual_ranks > 1) {
@@ -539,10 +510,10 @@ int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16
     }
     GM_TRY(dist_sparse_solve_wide(c, root));
     if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;
-    c->engine = GM_ENGINE_DIST_SPARSE;
     c->stats.engine = GM_ENGINE_DIST_SPARSE;
     c->stats.world = c->world > 1 ? c->world : std::max(1, c->virtual_ranks);
     c->solved = true;
+    c->solved_by = &dist_sparse_engine;   // digest and histogram go the common way
     if (n_positions) *n_positions = c->n_positions;
     if (root_record) *root_record = c->root_record;
     return GM_OK;
@@ -604,6 +575,7 @@ int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *o
     if (c->game != GM_GAME_GRAPH) { set_error("gm_solve_graph needs a GM_GAME_GRAPH context"); return GM_E_GAME; }
     // from here on a failure leaves the context without a table: the one it held is not this graph's
     c->solved = false;
+    c->solved_by = nullptr;
     c->hist_is_kept = false;
     if (!prim || !off) { set_error("gm_solve_graph needs primitive and child_off"); return GM_E_ARG; }
     if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
@@ -615,9 +587,9 @@ int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *o
     c->stats = gm_stats_t{};
     c->stats.world = 1;
     GM_TRY(graph_solve(c, n, prim, off, kid));
-    c->engine = GM_ENGINE_GRAPH;
     c->stats.engine = GM_ENGINE_GRAPH;
     c->solved = true;
+    c->solved_by = &graph_engine;
     if (root_record) *root_record = c->root_record;
     return GM_OK;
 }
@@ -633,13 +605,7 @@ int gm_export(gm_ctx *h, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t 
     if (!n || (keys && !recs)) return GM_E_ARG;
     Ctx *c = &h->c;
     GM_HIP(hipSetDevice(c->device));
-    if (c->engine == GM_ENGINE_GRAPH) return graph_export(c, keys, recs, cap, n);
-    if (c->engine == GM_ENGINE_DENSE)
-        return c->game == GM_GAME_SUBTRACT ? dense_sub_export(c, keys, recs, cap, n)
-                                           : small_dense_export(c, keys, recs, cap, n);
-    if (c->engine == GM_ENGINE_DIST_DENSE) return dist_sub_export(c, keys, recs, cap, n);
-    if (c->engine == GM_ENGINE_DIST_SPARSE) return dist_sparse_export(c, keys, recs, cap, n);
-    return sparse_export(c, keys, recs, cap, n);
+    return c->solved_by->export_(c, keys, recs, cap, n);
 }
 
 int gm_query(gm_ctx *h, const uint64_t *keys, uint16_t *recs, uint64_t n) {
@@ -647,12 +613,7 @@ int gm_query(gm_ctx *h, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     if (n && (!keys || !recs)) return GM_E_ARG;
     Ctx *c = &h->c;
     GM_HIP(hipSetDevice(c->device));
-    if (c->engine == GM_ENGINE_GRAPH) return graph_query(c, keys, recs, n);
-    if (c->engine == GM_ENGINE_DENSE)
-        return c->game == GM_GAME_SUBTRACT ? dense_sub_query(c, keys, recs, n) : small_dense_query(c, keys, recs, n);
-    if (c->engine == GM_ENGINE_DIST_DENSE) return dist_sub_query(c, keys, recs, n);
-    if (c->engine == GM_ENGINE_DIST_SPARSE) return dist_sparse_query(c, keys, recs, n);
-    return sparse_query(c, keys, recs, n);
+    return c->solved_by->query(c, keys, recs, n);
 }
 
 int gm_digest(gm_ctx *h, uint64_t *digest, uint64_t *n) {
@@ -660,12 +621,7 @@ int gm_digest(gm_ctx *h, uint64_t *digest, uint64_t *n) {
     if (!digest || !n) return GM_E_ARG;
     Ctx *c = &h->c;
     GM_HIP(hipSetDevice(c->device));
-    if (c->engine == GM_ENGINE_GRAPH) return graph_digest(c, digest, n);
-    if (c->engine == GM_ENGINE_DENSE)
-        return c->game == GM_GAME_SUBTRACT ? dense_sub_digest(c, digest, n) : small_dense_digest(c, digest, n);
-    if (c->engine == GM_ENGINE_DIST_DENSE) return dist_sub_digest(c, digest, n);
-    if (c->engine == GM_ENGINE_DIST_SPARSE) return dist_sparse_digest(c, digest, n);
-    return sparse_digest(c, digest, n);
+    return c->solved_by->digest(c, digest, n);
 }
 
 int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) {
@@ -678,14 +634,7 @@ int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) 
         // the census of the counts == NULL query just before: one pass over the table per pair
         for (int v = 0; v < 3; v++) H.v[v].swap(c->hist_kept[v]);
     } else {
-        int rc;
-        if (c->engine == GM_ENGINE_GRAPH) rc = graph_histogram(c, &H);
-        else if (c->engine == GM_ENGINE_DENSE)
-            rc = c->game == GM_GAME_SUBTRACT ? dense_sub_histogram(c, &H) : small_dense_histogram(c, &H);
-        else if (c->engine == GM_ENGINE_DIST_DENSE) rc = dist_sub_histogram(c, &H);
-        else if (c->engine == GM_ENGINE_DIST_SPARSE) rc = dist_sparse_histogram(c, &H);
-        else rc = sparse_histogram(c, &H);
-        if (rc != GM_OK) return rc;
+        GM_TRY(c->solved_by->histogram(c, &H));
     }
     c->hist_is_kept = false;
     const int nr = (int)H.n_rem();
@@ -730,11 +679,11 @@ int gm_adopt_buffer(gm_ctx *h, int role, void *p, uint64_t bytes) {
 int gm_dense_table(gm_ctx *h, void **p, uint64_t *bytes) {
     GM_TRY(need_solved(h));
     if (!p || !bytes) return GM_E_ARG;
-    if (h->c.engine != GM_ENGINE_DENSE || h->c.game != GM_GAME_SUBTRACT) {
+    if (!h->c.solved_by->table) {
         set_error("only the SUBTRACT dense path has a dense table");
         return GM_E_STATE;
     }
-    return dense_sub_table(&h->c, p, bytes);
+    return h->c.solved_by->table(&h->c, p, bytes);
 }
 
 int gm_dist_plan(int heaps, int world, int rank, const int32_t *opts, int what, int axis, uint32_t *off,
@@ -757,7 +706,7 @@ int gm_rank_stats(gm_ctx *h, double *kernel_ms, uint64_t *boxes, uint64_t *recv_
     GM_TRY(need_solved(h));
     if (!n) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (c->engine != GM_ENGINE_DENSE || !c->dbox_active || !c->dist_box) { *n = 0; return GM_OK; }
+    if (c->solved_by != &dist_box_engine) { *n = 0; return GM_OK; }   // ranks: the split box engine's
     return dist_box_rank_stats(c, kernel_ms, boxes, recv_bytes, cap, n);
 }
 
@@ -765,7 +714,7 @@ int gm_rank_op_ms(gm_ctx *h, int rank, double *ms, int cap, int *n) {
     GM_TRY(need_solved(h));
     if (!n) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (c->engine != GM_ENGINE_DENSE || !c->dbox_active || !c->dist_box) { *n = 0; return GM_OK; }
+    if (c->solved_by != &dist_box_engine) { *n = 0; return GM_OK; }   // ranks: the split box engine's
     return dist_box_op_ms(c, rank, ms, cap, n);
 }
 

@@ -5,6 +5,7 @@
 
 #include <stdarg.h>
 #include <stdio.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -61,6 +62,7 @@ struct DistBox;
 struct DistSparse;
 struct Graph;
 struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
+struct Engine;
 
 struct Ctx {
     int game = 0;
@@ -110,7 +112,7 @@ struct Ctx {
 
     // results
     bool solved = false;
-    int engine = 0;          // engine used by the last solve
+    const Engine *solved_by = nullptr;   // the engine whose table the context holds (set with solved)
     uint64_t root = 0;
     uint64_t n_positions = 0;
     uint16_t root_record = REC_UNSOLVED;
@@ -129,32 +131,45 @@ struct Ctx {
 
     DenseSub *dsub = nullptr;
     DenseBox *dbox = nullptr;   // the box engine (GM_OPT_SUB_INTERLEAVE 20, 8 heaps)
-    bool dbox_active = false;   // the last dense SUBTRACT solve used dbox
     SmallDense *sd = nullptr;
     Sparse *sp = nullptr;
     DistSub *dist_sub = nullptr;
-    DistBox *dist_box = nullptr;  // the box engine split over ranks (dist_box.hip), reached through dense_box_*
+    DistBox *dist_box = nullptr;  // the box engine split over ranks (dist_box.hip)
     DistSparse *dist_sp = nullptr;
     Graph *graph = nullptr;
 };
 
-// engines (each returns GM_OK or a GM_E_* code)
-int dense_sub_solve(Ctx *c, uint64_t root);
-int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dense_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int dense_sub_histogram(Ctx *c, Hist *out);
-void dense_sub_free(Ctx *c);
-int dense_sub_table(Ctx *c, void **p, uint64_t *bytes);
-// the box-tiled engine for 8 heaps (dense_box.hip), reached through dense_sub_*
-int dense_box_solve(Ctx *c, uint64_t root);
-int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dense_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int dense_box_histogram(Ctx *c, Hist *out);
-int dense_box_table(Ctx *c, void **p, uint64_t *bytes);
-void dense_box_free(Ctx *c);
-// shared with the split box engine (dist_box.hip)
+// One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
+// record next to its functions; gm_solve picks one per solve from the context's options
+// (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
+// of the solved table (export, query, digest, histogram, dense table, rank stats) goes through it.
+struct Engine {
+    int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
+    int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
+    int (*export_)(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
+    int (*query)(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
+    int (*digest)(Ctx *c, uint64_t *digest, uint64_t *n);
+    int (*histogram)(Ctx *c, Hist *out);
+    int (*table)(Ctx *c, void **p, uint64_t *bytes);   // null: the engine has no dense table
+    void (*free_)(Ctx *c);
+};
+// A record is host data, defined in the host pass only: the device pass of a translation unit
+// would emit a const record too, with references to the host functions it names.
+#ifdef __HIP_DEVICE_COMPILE__
+#define GM_ENGINE_RECORD(name, ...)
+#else
+#define GM_ENGINE_RECORD(name, ...) const Engine name = {__VA_ARGS__};
+#endif
+extern const Engine graph_engine;         // graph.hip
+extern const Engine small_dense_engine;   // small_dense.hip
+extern const Engine dense_sub_engine;     // dense_sub.hip: the block engine
+extern const Engine dense_box_engine;     // dense_box.hip: the box-tiled engine for 8 heaps
+extern const Engine dist_box_engine;      // dist_box.hip: the box engine split over G ranks
+extern const Engine dist_sub_engine;      // dist_sub.hip: the block engine partitioned over ranks
+extern const Engine sparse_engine;        // sparse.hip
+extern const Engine dist_sparse_engine;   // dist_sparse.hip: the hash-sharded sparse engine
+
+// the box engine's pieces shared with the split box engine (dist_box.hip)
 uint64_t box_hilbert(uint32_t box);
 int box_grid_cap(int device);
 void box_launch_split_flow(uint32_t grid, const void *ranks, uint32_t nranks, uint32_t ep, uint32_t *err,
@@ -178,16 +193,10 @@ void box_launch_query(const uint8_t *const *tables, const uint8_t *owner, uint64
                       uint16_t *out, uint64_t n, hipStream_t s);
 void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc);
 void box_region_keys(uint64_t root, uint64_t *keys, uint64_t n);
-// the box engine split over G ranks (dist_box.hip)
-int dist_box_solve(Ctx *c, uint64_t root);
-int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dist_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int dist_box_histogram(Ctx *c, Hist *out);
-int dist_box_table(Ctx *c, void **p, uint64_t *bytes);
+constexpr uint64_t BOX_QUERY_CHUNK = 1ull << 26;   // keys on the device at a time in a box engine query
+// the split box engine's per-rank figures (gm_rank_stats, gm_rank_op_ms) and its plan (gm_box_plan)
 int dist_box_rank_stats(Ctx *c, double *kernel_ms, uint64_t *boxes, uint64_t *recv_bytes, int cap, int *n);
 int dist_box_op_ms(Ctx *c, int rank, double *ms, int cap, int *n);
-void dist_box_free(Ctx *c);
 int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int what, int axis, uint32_t *out,
                   uint64_t cap, uint64_t *n);
 
@@ -202,48 +211,16 @@ void launch_sub_tier_x(int high, uint32_t nblocks, uint8_t *table, const uint32_
 int sub_kernel_threads(const Ctx *c, int low);   // 0 = the 4-block interleaved kernel
 void sort_tiers_morton(std::vector<uint32_t> &order, const std::vector<uint32_t> &tier_off, int high, int mode);
 
-// partitioned dense solve: `world` ranks, real (RCCL, one per process) or virtual (loopback)
-int dist_sub_solve(Ctx *c, uint64_t root);
-int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int dist_sub_histogram(Ctx *c, Hist *out);
-void dist_sub_free(Ctx *c);
+// gm_dist_plan, gm_sparse_layout: host only
 int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what, int axis, uint32_t *off,
                   uint64_t off_cap, uint64_t *n_off, uint32_t *data, uint64_t data_cap, uint64_t *n_data);
-
-int dist_sparse_solve(Ctx *c, uint64_t root);
-int dist_sparse_solve_wide(Ctx *c, const K128 &root);
 int dist_sparse_layout(int G, int S, const uint64_t *mat, int r, uint64_t *seg, uint64_t *send_off,
                        uint64_t *recv_off, uint64_t *recv_seg);
+// 128-bit keys (gm_*_key) do not fit the record: the hash-sharded sparse engine's wide entry points
+int dist_sparse_solve_wide(Ctx *c, const K128 &root);
 int dist_sparse_export_wide(Ctx *c, K128 *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
 int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n);
-int dist_sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dist_sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int dist_sparse_histogram(Ctx *c, Hist *out);
-void dist_sparse_free(Ctx *c);
-
-int small_dense_solve(Ctx *c, uint64_t root);
-int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int small_dense_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int small_dense_histogram(Ctx *c, Hist *out);
-void small_dense_free(Ctx *c);
-
 int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid);
-int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int graph_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int graph_histogram(Ctx *c, Hist *out);
-void graph_free(Ctx *c);
-
-int sparse_solve(Ctx *c, uint64_t root);
-int sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
-int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n);
-int sparse_histogram(Ctx *c, Hist *out);
-void sparse_free(Ctx *c);
 
 double now_ms();
 
@@ -255,6 +232,65 @@ int dev_alloc(Ctx *c, void **p, uint64_t bytes);
 void dev_free(Ctx *c, void *p);
 bool trace_on();
 int ensure_comm(Ctx *c);   // the RCCL communicator of gm_set_comm's unique id (collective on first use)
+
+// A temporary device buffer of the read paths: plain hipMalloc / hipFree (not the dev_alloc
+// cache, which would change what a context holds on to), freed when it leaves scope, so a
+// GM_HIP / GM_TRY that returns early does not leak it.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(uint64_t n) {
+        GM_HIP(hipMalloc(&p, n * sizeof(T)));
+        return GM_OK;
+    }
+    operator T *() const { return p; }
+};
+
+// keys up, one launch over them, records down: the dense engines' queries.  launch(dk, dr, m)
+// enqueues the kernel for m keys; `chunk` bounds the keys on the device at a time.
+template <class L>
+inline int query_keys(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n, uint64_t chunk, L &&launch) {
+    if (!n) return GM_OK;
+    chunk = std::min(n, chunk);
+    DevBuf<uint64_t> dk;
+    DevBuf<uint16_t> dr;
+    GM_TRY(dk.alloc(chunk));
+    GM_TRY(dr.alloc(chunk));
+    for (uint64_t o = 0; o < n; o += chunk) {
+        const uint64_t m = std::min(chunk, n - o);
+        GM_HIP(hipMemcpyAsync(dk, keys + o, m * 8, hipMemcpyHostToDevice, c->stream));
+        launch(dk.p, dr.p, m);
+        GM_HIP(hipMemcpyAsync(recs + o, dr, m * 2, hipMemcpyDeviceToHost, c->stream));
+    }
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
+// call f with the context's game descriptor: the five games with 64-bit keys
+template <class C, class F>
+inline int with_desc(C *c, F &&f) {
+    switch (c->game) {
+    case GM_GAME_FOUR_TO_ONE: return f(c->f2o);
+    case GM_GAME_TTT: return f(c->ttt);
+    case GM_GAME_TOOT: return f(c->toot);
+    case GM_GAME_OTHELLO: return f(c->oth);
+    case GM_GAME_SUBTRACT: return f(c->sub);
+    }
+    set_error("unknown game");
+    return GM_E_GAME;
+}
+// as with_desc, and Othello 8x8 (K128 keys) for a wide context
+template <class C, class F>
+inline int with_desc_wide(C *c, F &&f) {
+    if (c->wide) return f(c->oth8);
+    return with_desc(c, f);
+}
 
 }  // namespace gm
 

@@ -91,6 +91,8 @@ __global__ void graph_hist_kernel(const uint16_t *__restrict__ score, uint64_t n
 
 static unsigned grid_of(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
 
+static void graph_free(Ctx *c);
+
 int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid) {
     graph_free(c);
     if (!n) { set_error("empty graph"); return GM_E_ARG; }
@@ -153,40 +155,30 @@ int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, co
     return GM_OK;
 }
 
-int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     Graph *g = c->graph;
     *n = g->n;
     if (!keys) return GM_OK;
     if (cap < g->n) { set_error("export buffer too small"); return GM_E_CAP; }
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&dr, g->n * 2));
+    DevBuf<uint16_t> dr;
+    GM_TRY(dr.alloc(g->n));
     hipLaunchKernelGGL(graph_records_kernel, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, c->stream, g->score,
-                       (const uint64_t *)nullptr, dr, g->n, g->n);
+                       (const uint64_t *)nullptr, dr.p, g->n, g->n);
     GM_HIP(hipMemcpyAsync(recs, dr, g->n * 2, hipMemcpyDeviceToHost, c->stream));
     GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dr);
     for (uint64_t i = 0; i < g->n; i++) keys[i] = i;
     return GM_OK;
 }
 
-int graph_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int graph_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     Graph *g = c->graph;
-    if (!n) return GM_OK;
-    uint64_t *dk;
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&dk, n * 8));
-    GM_HIP(hipMalloc(&dr, n * 2));
-    GM_HIP(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(graph_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, g->score, dk,
-                       dr, n, g->n);
-    GM_HIP(hipMemcpyAsync(recs, dr, n * 2, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    return GM_OK;
+    return query_keys(c, keys, recs, n, n, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
+        hipLaunchKernelGGL(graph_records_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, g->score, dk,
+                           dr, m, g->n);
+    });
 }
 
-int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+static int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     Graph *g = c->graph;
     GM_HIP(hipMemsetAsync(g->d_count, 0, 8, c->stream));
     hipLaunchKernelGGL(graph_digest_kernel, dim3(grid_of(g->n)), dim3(256), 0, c->stream, g->score, g->n, g->d_count);
@@ -202,7 +194,7 @@ int graph_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
 // bound it) and at most 0x3FFF, which a chain ending in a LOSS or TIE leaf reaches (score_overflows
 // lets the last step through): first the bins that fit in LDS, and for a graph deeper than those the
 // global bins
-int graph_histogram(Ctx *c, Hist *out) {
+static int graph_histogram(Ctx *c, Hist *out) {
     Graph *g = c->graph;
     const uint32_t full = (uint32_t)std::min<uint64_t>(g->n, MAX_REMOTENESS + 2), lds = HIST_LDS_BUDGET / 12;
     for (uint32_t nbin : {std::min(full, lds), full}) {
@@ -217,7 +209,7 @@ int graph_histogram(Ctx *c, Hist *out) {
     return GM_OK;
 }
 
-void graph_free(Ctx *c) {
+static void graph_free(Ctx *c) {
     Graph *g = c->graph;
     if (!g) return;
     for (void *p : {(void *)g->prim, (void *)g->off, (void *)g->kid, (void *)g->score, (void *)g->d_count,
@@ -227,5 +219,8 @@ void graph_free(Ctx *c) {
     delete g;
     c->graph = nullptr;
 }
+
+GM_ENGINE_RECORD(graph_engine, GM_ENGINE_GRAPH, nullptr, graph_export,
+                 graph_query, graph_digest, graph_histogram, nullptr, graph_free)
 
 }  // namespace gm

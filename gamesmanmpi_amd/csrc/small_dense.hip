@@ -78,7 +78,7 @@ __global__ __launch_bounds__(1024) void small_dense_kernel(D d, uint64_t root, i
     if (tid == 0) { info[0] = s_err; info[1] = s_cnt; info[2] = s_prim; }
 }
 
-int small_dense_solve(Ctx *c, uint64_t root) {
+static int small_dense_solve(Ctx *c, uint64_t root) {
     if (c->game != GM_GAME_TTT) { set_error("small dense engine supports tic-tac-toe only"); return GM_E_GAME; }
     SmallDense *s = c->sd;
     if (!s) {
@@ -113,7 +113,7 @@ int small_dense_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     SmallDense *s = c->sd;
     *n = c->n_positions;
     if (!keys) return GM_OK;
@@ -124,13 +124,13 @@ int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uin
     return GM_OK;
 }
 
-int small_dense_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int small_dense_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     SmallDense *s = c->sd;
     for (uint64_t i = 0; i < n; i++) recs[i] = keys[i] < s->slots ? s->h_rec[keys[i]] : REC_UNSOLVED;
     return GM_OK;
 }
 
-int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+static int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     SmallDense *s = c->sd;
     uint64_t d = 0, k = 0;
     for (uint32_t i = 0; i < s->slots; i++)
@@ -140,14 +140,14 @@ int small_dense_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
     return GM_OK;
 }
 
-int small_dense_histogram(Ctx *c, Hist *out) {
+static int small_dense_histogram(Ctx *c, Hist *out) {
     SmallDense *s = c->sd;
     for (uint32_t i = 0; i < s->slots; i++)
         if (s->h_rec[i] != REC_UNSOLVED) out->add(s->h_rec[i] >> 14, s->h_rec[i] & 0x3FFFu, 1);
     return GM_OK;
 }
 
-void small_dense_free(Ctx *c) {
+static void small_dense_free(Ctx *c) {
     SmallDense *s = c->sd;
     if (!s) return;
     if (s->d_rec) hipFree(s->d_rec);
@@ -155,5 +155,8 @@ void small_dense_free(Ctx *c) {
     delete s;
     c->sd = nullptr;
 }
+
+GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
+                 small_dense_query, small_dense_digest, small_dense_histogram, nullptr, small_dense_free)
 
 }  // namespace gm

@@ -31,7 +31,7 @@ struct Sparse {
     std::vector<SpTier> tiers;
     unsigned long long *d_counts = nullptr;   // per-tier frontier counts (device)
     uint64_t counts_cap = 0;
-    unsigned long long *d_scratch = nullptr;  // [0,S) edges, [9] interior count, [10] seen, [12] export cursor
+    unsigned long long *d_scratch = nullptr;  // [0,S) edges, [9] interior count, [10] seen
     uint32_t *d_err = nullptr;
     int64_t t_root = 0;
     uint64_t edges = 0;
@@ -656,6 +656,9 @@ static int probe_stats(Ctx *c, Sparse *sp) {
     return GM_OK;
 }
 
+static void sparse_free(Ctx *c);
+static int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
+
 template <class D>
 static int solve_with(Ctx *c, const D &d, uint64_t root) {
     constexpr int S = D::MAX_SKIP;
@@ -811,143 +814,37 @@ static int solve_with(Ctx *c, const D &d, uint64_t root) {
     return GM_OK;
 }
 
-// call f with the context's game descriptor
-template <class F>
-static int with_desc(Ctx *c, F &&f) {
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: return f(c->f2o);
-    case GM_GAME_TTT: return f(c->ttt);
-    case GM_GAME_TOOT: return f(c->toot);
-    case GM_GAME_OTHELLO: return f(c->oth);
-    case GM_GAME_SUBTRACT: return f(c->sub);
-    }
-    set_error("sparse engine: unknown game");
-    return GM_E_GAME;
+static int sparse_solve(Ctx *c, uint64_t root) {
+    return with_desc(c, [&](const auto &d) { return solve_with(c, d, root); });
 }
 
-int sparse_solve(Ctx *c, uint64_t root) {
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: return solve_with(c, c->f2o, root);
-    case GM_GAME_TTT: return solve_with(c, c->ttt, root);
-    case GM_GAME_TOOT: return solve_with(c, c->toot, root);
-    case GM_GAME_OTHELLO: return solve_with(c, c->oth, root);
-    case GM_GAME_SUBTRACT: return solve_with(c, c->sub, root);
-    }
-    set_error("sparse engine: unknown game");
-    return GM_E_GAME;
+static TierList<uint64_t> tier_list(const Sparse *sp) {
+    TierList<uint64_t> l;
+    for (auto &T : sp->tiers) l.push_back(&T);
+    return l;
 }
 
-template <class D>
-static void launch_query(Ctx *c, const D &d, Sparse *sp, ResRef *tabs, const uint64_t *dk, uint16_t *dr,
-                         uint64_t n) {
-    hipLaunchKernelGGL(query_kernel<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d, sp->t_root,
-                       tabs, (int)sp->tiers.size(), dk, dr, n);
-}
-
-int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    Sparse *sp = c->sp;
-    if (!n) return GM_OK;
-    std::vector<ResRef> h(sp->tiers.size());
-    for (size_t t = 0; t < h.size(); t++) h[t] = res_ref(sp, t);
-    ResRef *tabs;
-    uint64_t *dk;
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&tabs, std::max<size_t>(1, h.size()) * sizeof(ResRef)));
-    GM_HIP(hipMalloc(&dk, n * 8));
-    GM_HIP(hipMalloc(&dr, n * 2));
-    if (!h.empty()) GM_HIP(hipMemcpyAsync(tabs, h.data(), h.size() * sizeof(ResRef), hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, c->stream));
-    switch (c->game) {
-    case GM_GAME_FOUR_TO_ONE: launch_query(c, c->f2o, sp, tabs, dk, dr, n); break;
-    case GM_GAME_TTT: launch_query(c, c->ttt, sp, tabs, dk, dr, n); break;
-    case GM_GAME_TOOT: launch_query(c, c->toot, sp, tabs, dk, dr, n); break;
-    case GM_GAME_OTHELLO: launch_query(c, c->oth, sp, tabs, dk, dr, n); break;
-    case GM_GAME_SUBTRACT: launch_query(c, c->sub, sp, tabs, dk, dr, n); break;
-    }
-    GM_HIP(hipMemcpyAsync(recs, dr, n * 2, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    (void)hipFree(tabs);
-    return GM_OK;
-}
-
-int sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    Sparse *sp = c->sp;
-    uint64_t total = 0;
-    for (auto &T : sp->tiers) total += T.count_all;
-    *n = total;
-    if (!keys) return GM_OK;
-    if (cap < total) {
-        set_error("export buffer holds %llu, need %llu", (unsigned long long)cap, (unsigned long long)total);
-        return GM_E_CAP;
-    }
-    uint64_t *dk;
-    uint16_t *dr;
-    GM_HIP(hipMalloc(&dk, std::max<uint64_t>(1, total) * 8));
-    GM_HIP(hipMalloc(&dr, std::max<uint64_t>(1, total) * 2));
-    GM_HIP(hipMemsetAsync(sp->d_scratch + 12, 0, 8, c->stream));
-    GM_TRY(with_desc(c, [&](const auto &d) {
-        for (auto &T : sp->tiers)
-            if (T.count)
-                hipLaunchKernelGGL(res_gather_kernel<std::decay_t<decltype(d)>>, dim3(grid_for(T.cap)), dim3(256), 0,
-                                   c->stream, d, T.slots, T.cap, dk, dr, sp->d_scratch + 12);
-        return GM_OK;
-    }));
-    std::vector<uint64_t> hk(total);
-    std::vector<uint16_t> hr(total);
-    GM_HIP(hipMemcpyAsync(hk.data(), dk, total * 8, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipMemcpyAsync(hr.data(), dr, total * 2, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dk);
-    (void)hipFree(dr);
-    std::vector<uint64_t> idx(total);
-    for (uint64_t i = 0; i < total; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return hk[a] < hk[b]; });
-    for (uint64_t i = 0; i < total; i++) {
-        keys[i] = hk[idx[i]];
-        recs[i] = hr[idx[i]];
-    }
-    return GM_OK;
-}
-
-int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    Sparse *sp = c->sp;
-    GM_HIP(hipMemsetAsync(sp->d_scratch + 12, 0, 8, c->stream));
-    uint64_t total = 0;
-    for (auto &T : sp->tiers) total += T.count_all;
-    GM_TRY(with_desc(c, [&](const auto &d) {
-        for (auto &T : sp->tiers)
-            if (T.count)
-                hipLaunchKernelGGL(res_digest_kernel<std::decay_t<decltype(d)>>, dim3(grid_counted(T.cap)), dim3(256), 0,
-                                   c->stream, d, T.slots, T.cap, sp->d_scratch + 12);
-        return GM_OK;
-    }));
-    unsigned long long h;
-    GM_HIP(hipMemcpyAsync(&h, sp->d_scratch + 12, 8, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    *digest = h;
-    *n = total;
-    return GM_OK;
-}
-
-// remoteness is below the number of tiers walked: 3 x (tiers + 1) bins (hist_common.hpp)
-int sparse_histogram(Ctx *c, Hist *out) {
-    Sparse *sp = c->sp;
-    ScoreBins b;
-    GM_TRY(score_bins_begin(c, (uint32_t)sp->tiers.size() + 1, &b));
-    int rc = with_desc(c, [&](const auto &d) {
-        for (auto &T : sp->tiers)
-            if (T.count)
-                hipLaunchKernelGGL(res_hist_kernel<std::decay_t<decltype(d)>>, dim3(grid_counted(T.cap)), dim3(256),
-                                   b.lds_bytes, c->stream, d, T.slots, T.cap, b.d, b.nbin, b.use_lds);
-        return GM_OK;
+static int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+    return with_desc(c, [&](const auto &d) {
+        return tiers_query(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, keys, recs, n);
     });
-    const int rc2 = score_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
 }
 
-void sparse_free(Ctx *c) {
+static int sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    return with_desc(c, [&](const auto &d) { return tiers_export(c, d, tier_list(c->sp), keys, recs, cap, n); });
+}
+
+static int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+    return with_desc(c, [&](const auto &d) { return tiers_digest(c, d, tier_list(c->sp), digest, n); });
+}
+
+static int sparse_histogram(Ctx *c, Hist *out) {
+    return with_desc(c, [&](const auto &d) {
+        return tiers_histogram(c, d, tier_list(c->sp), c->sp->tiers.size(), out);
+    });
+}
+
+static void sparse_free(Ctx *c) {
     Sparse *sp = c->sp;
     if (!sp) return;
     for (auto &T : sp->tiers) free_tier(c, T);
@@ -961,5 +858,8 @@ void sparse_free(Ctx *c) {
     delete sp;
     c->sp = nullptr;
 }
+
+GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
+                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free)
 
 }  // namespace gm

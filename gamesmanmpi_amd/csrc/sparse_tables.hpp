@@ -572,4 +572,119 @@ inline void free_tier(Ctx *c, SpTierT<K> &T) {
     T = SpTierT<K>{};
 }
 
+// ----------------------------------------------------------------- readers
+// The host side of export, query, digest and histogram over tier tables: the one-GPU engine
+// passes its tiers, the sharded engine those of every rank it runs.
+template <class K>
+using TierList = std::vector<const SpTierT<K> *>;
+
+// every position of the tables (each representative's orbit expanded), sorted by key
+template <class D>
+inline int tiers_export(Ctx *c, const D &d, const TierList<key_t<D>> &tiers, key_t<D> *keys, uint16_t *recs,
+                        uint64_t cap, uint64_t *n) {
+    using K = key_t<D>;
+    uint64_t total = 0;
+    for (auto *T : tiers) total += T->count_all;
+    *n = total;
+    if (!keys) return GM_OK;
+    if (cap < total) {
+        set_error("export buffer holds %llu, need %llu", (unsigned long long)cap, (unsigned long long)total);
+        return GM_E_CAP;
+    }
+    DevBuf<K> dk;
+    DevBuf<uint16_t> dr;
+    DevBuf<unsigned long long> cur;
+    GM_TRY(dk.alloc(std::max<uint64_t>(1, total)));
+    GM_TRY(dr.alloc(std::max<uint64_t>(1, total)));
+    GM_TRY(cur.alloc(1));
+    GM_HIP(hipMemsetAsync(cur, 0, 8, c->stream));
+    for (auto *T : tiers)
+        if (T->count)
+            hipLaunchKernelGGL(res_gather_kernel<D>, dim3(grid_for(T->cap)), dim3(256), 0, c->stream, d, T->slots, T->cap,
+                               dk.p, dr.p, cur.p);
+    std::vector<K> hk(total);
+    std::vector<uint16_t> hr(total);
+    GM_HIP(hipMemcpyAsync(hk.data(), dk, total * sizeof(K), hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipMemcpyAsync(hr.data(), dr, total * 2, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    std::vector<uint64_t> idx(total);
+    for (uint64_t i = 0; i < total; i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return hk[a] < hk[b]; });
+    for (uint64_t i = 0; i < total; i++) {
+        keys[i] = hk[idx[i]];
+        recs[i] = hr[idx[i]];
+    }
+    return GM_OK;
+}
+
+template <class D>
+inline int tiers_digest(Ctx *c, const D &d, const TierList<key_t<D>> &tiers, uint64_t *digest, uint64_t *n) {
+    DevBuf<unsigned long long> acc;
+    GM_TRY(acc.alloc(1));
+    GM_HIP(hipMemsetAsync(acc, 0, 8, c->stream));
+    uint64_t total = 0;
+    for (auto *T : tiers) {
+        total += T->count_all;
+        if (T->count)
+            hipLaunchKernelGGL(res_digest_kernel<D>, dim3(grid_counted(T->cap)), dim3(256), 0, c->stream, d, T->slots,
+                               T->cap, acc.p);
+    }
+    unsigned long long h;
+    GM_HIP(hipMemcpyAsync(&h, acc, 8, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    *digest = h;
+    *n = total;
+    return GM_OK;
+}
+
+// census of the tables; remoteness is below the number of tiers walked (`depth`): 3 x (depth + 1)
+// bins (hist_common.hpp)
+template <class D>
+inline int tiers_histogram(Ctx *c, const D &d, const TierList<key_t<D>> &tiers, size_t depth, Hist *out) {
+    ScoreBins b;
+    GM_TRY(score_bins_begin(c, (uint32_t)depth + 1, &b));
+    for (auto *T : tiers)
+        if (T->count)
+            hipLaunchKernelGGL(res_hist_kernel<D>, dim3(grid_counted(T->cap)), dim3(256), b.lds_bytes, c->stream, d,
+                               T->slots, T->cap, b.d, b.nbin, b.use_lds);
+    return score_bins_end(c, &b, out);
+}
+
+// One group of tier tables a query looks in: a tier per table from the root's (t_root) on.  A
+// key is in at most one group (the sharded engine: one per rank); keys in none stay REC_UNSOLVED.
+template <class K>
+struct TierGroup {
+    const std::vector<SpTierT<K>> *tiers;
+    int64_t t_root;
+};
+
+template <class D>
+inline int tiers_query(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>> &groups, const key_t<D> *keys,
+                       uint16_t *recs, uint64_t n) {
+    using K = key_t<D>;
+    using Res = typename KT<K>::Res;
+    if (!n) return GM_OK;
+    DevBuf<K> dk;
+    DevBuf<uint16_t> dr;
+    GM_TRY(dk.alloc(n));
+    GM_TRY(dr.alloc(n));
+    GM_HIP(hipMemcpyAsync(dk, keys, n * sizeof(K), hipMemcpyHostToDevice, c->stream));
+    std::vector<uint16_t> part(n);
+    for (uint64_t i = 0; i < n; i++) recs[i] = REC_UNSOLVED;
+    for (auto &g : groups) {
+        std::vector<Res> h(g.tiers->size());
+        for (size_t t = 0; t < h.size(); t++) h[t] = res_ref_of((*g.tiers)[t]);
+        DevBuf<Res> tabs;
+        GM_TRY(tabs.alloc(std::max<size_t>(1, h.size())));
+        if (!h.empty()) GM_HIP(hipMemcpyAsync(tabs, h.data(), h.size() * sizeof(Res), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(query_kernel<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d, g.t_root,
+                           tabs.p, (int)h.size(), dk.p, dr.p, n);
+        GM_HIP(hipMemcpyAsync(part.data(), dr, n * 2, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));
+        for (uint64_t i = 0; i < n; i++)
+            if (part[i] != REC_UNSOLVED) recs[i] = part[i];
+    }
+    return GM_OK;
+}
+
 }  // namespace gm
