@@ -49,7 +49,7 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
-           "gm_histogram")
+           "gm_histogram", "gm_verify", "gm_poke")
 
 
 class GMError(RuntimeError):
@@ -81,6 +81,27 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Verify(ctypes.Structure):
+    """gm_verify_t (include/gmsolve.h)."""
+    _fields_ = [
+        ("checked", ctypes.c_uint64),
+        ("bad_key", ctypes.c_uint64),
+        ("misplaced", ctypes.c_uint64),
+        ("bad_primitive", ctypes.c_uint64),
+        ("missing_child", ctypes.c_uint64),
+        ("bad_value", ctypes.c_uint64),
+        ("child_lookups", ctypes.c_uint64),
+        ("root_ok", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+    CLASSES = ("bad_key", "misplaced", "bad_primitive", "missing_child", "bad_value")
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+        d["n_bad"] = sum(d[k] for k in self.CLASSES)
+        return d
 
 
 _lib = None
@@ -116,6 +137,8 @@ def lib():
         "gm_query": (ctypes.c_int, [vp, vp, vp, u64]),
         "gm_digest": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "gm_histogram": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int), P(u64)]),
+        "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
+        "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
         "gm_stats": (ctypes.c_int, [vp, P(Stats)]),
         "gm_tier_counts": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int)]),
         "gm_adopt_buffer": (ctypes.c_int, [vp, ctypes.c_int, vp, u64]),

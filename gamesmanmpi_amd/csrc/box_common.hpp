@@ -52,6 +52,17 @@ GM_HD uint32_t box_key_of_index(uint32_t x) {
     }
     return k;
 }
+// the table index of the position that differs from the one at index x in heap `heap` alone,
+// which holds h there: the heap's two fields replaced, no other heap decoded (gm_verify walks
+// up to 16 children per position)
+GM_HD uint32_t box_index_with_heap(uint32_t x, int heap, uint32_t h) {
+    if (heap < 4) {
+        const int o = 4 + 2 * heap, b = 12 + 2 * heap;
+        return (x & ~((3u << o) | (3u << b))) | ((h & 3u) << o) | ((h >> 2) << b);
+    }
+    const int o = heap - 4, b = 20 + 3 * (heap - 4);
+    return (x & ~((1u << o) | (7u << b))) | ((h & 1u) << o) | ((h >> 1) << b);
+}
 GM_HD int box_coord(uint32_t box, int dim) {
     return dim < 4 ? (int)((box >> (2 * dim)) & 3u) : (int)((box >> (8 + 3 * (dim - 4))) & 7u);
 }

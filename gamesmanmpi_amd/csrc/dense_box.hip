@@ -44,6 +44,7 @@
 // .amdhsa_float_denorm_mode_16_64 3).
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1798,6 +1799,25 @@ static int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
     return GM_OK;
 }
 
+// gm_verify over the region's boxes, each 4 KiB of the table (verify_common.hpp)
+static int dense_box_verify(Ctx *c, const VerifyDev &v) {
+    DenseBox *d = c->dbox;
+    return byte_verify_launch<1>(c, v, d->d_tables, nullptr, d->d_boxes, d->boxes.size(), 12, 0, 8);
+}
+
+static int dense_box_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    DenseBox *d = c->dbox;
+    bool in = words[0] < (1ull << 32);
+    for (int j = 0; j < 8 && in; j++) in = ((words[0] >> (4 * j)) & 15u) <= ((c->root >> (4 * j)) & 15u);
+    if (!in) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const int code = code_of_record(rec);
+    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
+    const uint8_t b = (uint8_t)code;
+    GM_HIP(hipMemcpyAsync(d->table + box_index_of_key((uint32_t)words[0]), &b, 1, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
 static void dense_box_free(Ctx *c) {
     DenseBox *d = c->dbox;
     if (!d) return;
@@ -1813,6 +1833,7 @@ static void dense_box_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
-                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_table, dense_box_free)
+                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_table, dense_box_free,
+                 dense_box_verify, dense_box_poke)
 
 }  // namespace gm

@@ -34,6 +34,7 @@
 // edge: 1 + 14.5 = 15.5 B per position at 8 heaps (31 B with u16 records).
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -1237,6 +1238,37 @@ static int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {
     return GM_OK;
 }
 
+// gm_verify: the table is one unit of 16^heaps bytes, slot = key (verify_common.hpp)
+static int dense_sub_verify(Ctx *c, const VerifyDev &v) {
+    DenseSub *d = c->dsub;
+    DevBuf<const uint8_t *> tabs;
+    GM_TRY(tabs.alloc(1));
+    const uint8_t *t = d->table;
+    GM_HIP(hipMemcpyAsync(tabs, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
+    GM_TRY(byte_verify_launch<0>(c, v, tabs.p, nullptr, nullptr, 1, 4 * d->heaps, 0, d->heaps));
+    GM_HIP(hipStreamSynchronize(c->stream));   // tabs leaves scope
+    return GM_OK;
+}
+
+// a key of the root's region of a SUBTRACT table of `heaps` heaps
+static bool sub_key_held(const Ctx *c, uint64_t k, int heaps) {
+    if (heaps < 16 && (k >> (4 * heaps))) return false;
+    for (int j = 0; j < heaps; j++)
+        if (((k >> (4 * j)) & 15u) > ((c->root >> (4 * j)) & 15u)) return false;
+    return true;
+}
+
+static int dense_sub_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    DenseSub *d = c->dsub;
+    if (!sub_key_held(c, words[0], d->heaps)) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const int code = code_of_record(rec);
+    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
+    const uint8_t b = (uint8_t)code;
+    GM_HIP(hipMemcpyAsync(d->table + words[0], &b, 1, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
 static void dense_sub_free(Ctx *c) {
     DenseSub *d = c->dsub;
     if (!d) return;
@@ -1251,6 +1283,7 @@ static void dense_sub_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
-                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_table, dense_sub_free)
+                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_table, dense_sub_free,
+                 dense_sub_verify, dense_sub_poke)
 
 }  // namespace gm

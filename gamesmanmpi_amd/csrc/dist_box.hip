@@ -44,6 +44,7 @@
 // comes after the record it waits for.
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1493,6 +1494,35 @@ static int dist_box_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
+// gm_verify over every virtual rank's own boxes; each code, a position's own and its children's,
+// is read from its box's holder as box_launch_query reads it (d_owner, d_tables)
+static int dist_box_verify(Ctx *c, const VerifyDev &v) {
+    DistBox *d = c->dist_box;
+    for (auto &R : d->ranks)
+        if (R.table) GM_TRY(byte_verify_launch<1>(c, v, d->d_tables, d->d_owner, R.d_boxes, R.boxes.size(), 12, 0, 8));
+    return GM_OK;
+}
+
+static int dist_box_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    DistBox *d = c->dist_box;
+    bool in = words[0] < (1ull << 32);
+    for (int j = 0; j < 8 && in; j++) in = ((words[0] >> (4 * j)) & 15u) <= ((c->root >> (4 * j)) & 15u);
+    const uint32_t idx = in ? box_index_of_key((uint32_t)words[0]) : 0u;
+    uint8_t own = 0xFF;
+    const uint8_t *tab = nullptr;
+    if (in) {
+        GM_HIP(hipMemcpy(&own, d->d_owner + (idx >> 12), 1, hipMemcpyDeviceToHost));
+        if (own != 0xFF) GM_HIP(hipMemcpy(&tab, d->d_tables + own, sizeof tab, hipMemcpyDeviceToHost));
+    }
+    if (!tab) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const int code = code_of_record(rec);
+    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
+    const uint8_t b = (uint8_t)code;
+    GM_HIP(hipMemcpyAsync((uint8_t *)tab + idx, &b, 1, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
 static int dist_box_table(Ctx *c, void **p, uint64_t *bytes) {
     DistBox *d = c->dist_box;
     *p = d->ranks[0].table;
@@ -1657,6 +1687,7 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
 }
 
 GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
-                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_table, dist_box_free)
+                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_table, dist_box_free,
+                 dist_box_verify, dist_box_poke)
 
 }  // namespace gm

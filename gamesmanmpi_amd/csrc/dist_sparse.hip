@@ -1328,6 +1328,31 @@ int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n)
     return query_ranks(c, c->oth8, keys, recs, n);
 }
 
+// gm_verify / gm_poke over every virtual rank's tables (one group per owner rank, in rank order);
+// a rank of a multi-process solve holds one group of G and is refused in gm_api.hip
+template <class K>
+static std::vector<TierGroup<K>> rank_groups(Ctx *c) {
+    auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
+    std::vector<TierGroup<K>> groups;
+    for (auto &R : d->ranks) groups.push_back({&R.tiers, d->t_root});
+    return groups;
+}
+
+static int dist_sparse_verify(Ctx *c, const VerifyDev &v) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        return tiers_verify(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), v);
+    });
+}
+
+static int dist_sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    if (c->wide) {
+        K128 k;
+        if (!DescOthello8::from_words(words, &k)) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+        return tiers_poke(c, c->oth8, rank_groups<K128>(c), k, rec);
+    }
+    return with_desc(c, [&](const auto &desc) { return tiers_poke(c, desc, rank_groups<uint64_t>(c), words[0], rec); });
+}
+
 template <class K>
 static void free_ranks(Ctx *c, DistSparseK<K> *d) {
     for (auto &R : d->ranks) {
@@ -1361,6 +1386,7 @@ static void dist_sparse_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
-                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, nullptr, dist_sparse_free)
+                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, nullptr, dist_sparse_free,
+                 dist_sparse_verify, dist_sparse_poke)
 
 }  // namespace gm

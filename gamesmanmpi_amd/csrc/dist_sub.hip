@@ -61,6 +61,7 @@
 // cross-rank wait is enqueued after the record it waits for.
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 
 #include <mutex>
 
@@ -821,6 +822,48 @@ static int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t
     return GM_OK;
 }
 
+// the position in d->ranks of the rank that owns high part H (0xFF: not one of this context's)
+static uint8_t holder_of(const DistSub *d, uint64_t H) {
+    const int own = owner_of(d, H);
+    for (size_t i = 0; i < d->ranks.size(); i++)
+        if (d->ranks[i].rank == own) return (uint8_t)i;
+    return 0xFF;
+}
+
+// gm_verify over the blocks the virtual ranks own (verify_common.hpp): a block is 16^low
+// contiguous bytes of its owner's table, and every code -- a position's own and its
+// children's -- is read from its owner's table, as dist_sub_query reads it
+static int dist_sub_verify(Ctx *c, const VerifyDev &v) {
+    DistSub *d = c->dist_sub;
+    std::vector<uint8_t> own(1ull << (4 * d->high));
+    for (uint64_t H = 0; H < own.size(); H++) own[H] = holder_of(d, H);
+    std::vector<const uint8_t *> tabs;
+    for (auto &R : d->ranks) tabs.push_back(R.table);
+    DevBuf<uint8_t> d_own;
+    DevBuf<const uint8_t *> d_tabs;
+    GM_TRY(d_own.alloc(own.size()));
+    GM_TRY(d_tabs.alloc(tabs.size()));
+    GM_HIP(hipMemcpyAsync(d_own, own.data(), own.size(), hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipMemcpyAsync(d_tabs, tabs.data(), tabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    for (auto &R : d->ranks)
+        GM_TRY(byte_verify_launch<0>(c, v, d_tabs.p, d_own.p, R.dlist, R.off.back(), 4 * d->low, 4 * d->low, d->heaps));
+    GM_HIP(hipStreamSynchronize(c->stream));   // the temporaries leave scope
+    return GM_OK;
+}
+
+static int dist_sub_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    DistSub *d = c->dist_sub;
+    const uint64_t k = words[0];
+    const bool in = !(k >> (4 * d->heaps)) && in_box(k, c->root, d->heaps);
+    const uint8_t h = in ? holder_of(d, k >> (4 * d->low)) : 0xFF;
+    if (h == 0xFF) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const int code = code_of_record(rec);
+    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
+    const uint8_t b = (uint8_t)code;
+    GM_HIP(hipMemcpy(d->ranks[h].table + k, &b, 1, hipMemcpyHostToDevice));
+    return GM_OK;
+}
+
 static void dist_sub_free(Ctx *c) {
     DistSub *d = c->dist_sub;
     if (!d) return;
@@ -933,6 +976,7 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
 }
 
 GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
-                 dist_sub_query, dist_sub_digest, dist_sub_histogram, nullptr, dist_sub_free)
+                 dist_sub_query, dist_sub_digest, dist_sub_histogram, nullptr, dist_sub_free,
+                 dist_sub_verify, dist_sub_poke)
 
 }  // namespace gm

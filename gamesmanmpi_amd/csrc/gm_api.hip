@@ -1,6 +1,7 @@
 // gm_api.hip -- the C ABI (include/gmsolve.h): contexts, dispatch, errors.
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 
 #include <chrono>
 #include <stdlib.h>
@@ -337,6 +338,24 @@ int gm_expand_host(gm_ctx *h, uint64_t key, uint64_t *children, int cap, int *n,
         if (p == UNDECIDED) k = d.children(key, kids);
         return GM_OK;
     }));
+    if (c->game == GM_GAME_OTHELLO && k > 1) {
+        // the promised gen_moves order: squares x outer, y inner (othello_bit_new.py:137-143), where
+        // visit() walks the rotated plane's lowest bit first.  The square played is the one bit
+        // the occupied plane gains: plane bit A - 1 - (L y + x)  (as gm_expand_host_key, 8x8)
+        const DescOthello &o = c->oth;
+        auto occ = [&](uint64_t q) { return o.wplane(q) | o.bplane(q); };
+        auto rank = [&](uint64_t ch) {
+            const int j = o.A - 1 - __builtin_ctz(occ(ch) ^ occ(key));
+            return o.L * (j % o.L) + j / o.L;
+        };
+        for (int i = 1; i < k; i++) {
+            const uint64_t ch = kids[i];
+            const int r = rank(ch);
+            int at = i;
+            for (; at > 0 && rank(kids[at - 1]) > r; at--) kids[at] = kids[at - 1];
+            kids[at] = ch;
+        }
+    }
     *prim = p;
     *tier = t;
     *n = k;
@@ -508,6 +527,7 @@ int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16
         if (!c->have_uid) { set_error("a %d-rank solve needs gm_set_comm with a unique id", c->world); return GM_E_COMM; }
         if (c->sparse_transport != 1) GM_TRY(ensure_comm(c));
     }
+    c->root_wide = root;
     GM_TRY(dist_sparse_solve_wide(c, root));
     if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;
     c->stats.engine = GM_ENGINE_DIST_SPARSE;
@@ -649,6 +669,81 @@ int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) 
     for (int v = 0; v < 3; v++)
         for (int r = 0; r < cap; r++) counts[(size_t)v * cap + r] = (size_t)r < H.v[v].size() ? H.v[v][r] : 0;
     return GM_OK;
+}
+
+// a rank of a multi-process solve holds its share of the table only
+static int need_whole_table(Ctx *c, const char *what) {
+    if (c->world > 1) {
+        set_error("%s needs the whole table in one context: this is rank %d of a %d-process solve, which does not hold "
+                  "the tables of its children's owners (virtual ranks are supported)", what, c->rank, c->world);
+        return GM_E_STATE;
+    }
+    return GM_OK;
+}
+
+int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap, uint64_t *n_bad) {
+    GM_TRY(need_solved(h));
+    if (!out) { set_error("out is NULL"); return GM_E_ARG; }
+    Ctx *c = &h->c;
+    GM_TRY(need_whole_table(c, "gm_verify"));
+    GM_HIP(hipSetDevice(c->device));
+    const uint64_t want = bad_key_words ? cap : 0;
+    const uint64_t key_bytes = c->wide ? sizeof(K128) : 8;
+    gm_verify_t r{};
+    std::vector<unsigned char> raw;
+    uint64_t nb = 0;
+    // the list holds VF_FIRST_CAP keys at first; a table with more offenders, when the caller
+    // has room for them, is checked again into a list of the right size
+    for (uint64_t dev_cap = std::min(want, VF_FIRST_CAP);;) {
+        VerifyRun run;
+        GM_TRY(verify_begin(c, dev_cap, key_bytes, &run));
+        const int rc = c->solved_by->verify(c, run.dev);
+        const int rc2 = verify_end(c, &run, &r, &raw);
+        if (rc != GM_OK) return rc;
+        if (rc2 != GM_OK) return rc2;
+        nb = r.bad_key + r.misplaced + r.bad_primitive + r.missing_child + r.bad_value;
+        if (nb <= dev_cap || dev_cap >= want) break;
+        dev_cap = std::min(want, nb);
+    }
+    // the root: stored, with the record the solve returned
+    uint16_t rr = REC_UNSOLVED;
+    if (c->wide) GM_TRY(dist_sparse_query_wide(c, &c->root_wide, &rr, 1));
+    else GM_TRY(c->solved_by->query(c, &c->root, &rr, 1));
+    r.root_ok = rr != REC_UNSOLVED && rr == c->root_record;
+    *out = r;
+    if (n_bad) *n_bad = nb;
+    if (!want) return GM_OK;
+    // ascending ABI key order (a wide key: the position string as one integer)
+    const int W = c->wide ? WIDE_WORDS : 1;
+    const uint64_t n = raw.size() / key_bytes;
+    std::vector<uint64_t> w((size_t)W * n);
+    for (uint64_t i = 0; i < n; i++) {
+        if (c->wide) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
+        else w[i] = ((const uint64_t *)raw.data())[i];
+    }
+    std::vector<uint64_t> idx(n);
+    for (uint64_t i = 0; i < n; i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+        for (int j = W - 1; j >= 0; j--) {
+            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
+            if (x != y) return x < y;
+        }
+        return false;
+    });
+    for (uint64_t i = 0; i < n; i++)
+        for (int j = 0; j < W; j++) bad_key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
+    return GM_OK;
+}
+
+int gm_poke(gm_ctx *h, const uint64_t *key_words, uint16_t record) {
+    GM_TRY(need_solved(h));
+    if (!key_words) { set_error("key_words is NULL"); return GM_E_ARG; }
+    if (record != REC_UNSOLVED && (record >> 14) > TIE) { set_error("gm_poke: not a record"); return GM_E_ARG; }
+    Ctx *c = &h->c;
+    GM_TRY(need_whole_table(c, "gm_poke"));
+    GM_HIP(hipSetDevice(c->device));
+    c->hist_is_kept = false;
+    return c->solved_by->poke(c, key_words, record);
 }
 
 int gm_stats(gm_ctx *h, gm_stats_t *out) {

@@ -62,6 +62,7 @@ struct DistBox;
 struct DistSparse;
 struct Graph;
 struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
+struct VerifyDev;   // verify_common.hpp: the device accumulator of gm_verify
 struct Engine;
 
 struct Ctx {
@@ -114,6 +115,7 @@ struct Ctx {
     bool solved = false;
     const Engine *solved_by = nullptr;   // the engine whose table the context holds (set with solved)
     uint64_t root = 0;
+    K128 root_wide{0, 0};    // a wide context's root (gm_solve_key), for gm_verify's root check
     uint64_t n_positions = 0;
     uint16_t root_record = REC_UNSOLVED;
     gm_stats_t stats{};
@@ -142,7 +144,7 @@ struct Ctx {
 // One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
 // record next to its functions; gm_solve picks one per solve from the context's options
 // (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
-// of the solved table (export, query, digest, histogram, dense table, rank stats) goes through it.
+// of the solved table (export, query, digest, histogram, verify, dense table, rank stats) goes through it.
 struct Engine {
     int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
     int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
@@ -152,6 +154,8 @@ struct Engine {
     int (*histogram)(Ctx *c, Hist *out);
     int (*table)(Ctx *c, void **p, uint64_t *bytes);   // null: the engine has no dense table
     void (*free_)(Ctx *c);
+    int (*verify)(Ctx *c, const VerifyDev &v);         // gm_verify: every stored position into the accumulator
+    int (*poke)(Ctx *c, const uint64_t *words, uint16_t rec);   // gm_poke: one stored record overwritten (test hook)
 };
 // A record is host data, defined in the host pass only: the device pass of a translation unit
 // would emit a const record too, with references to the host functions it names.

@@ -14,6 +14,7 @@
 // reading a child in the round it is written is benign.
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 
 #include <algorithm>
 
@@ -209,6 +210,47 @@ static int graph_histogram(Ctx *c, Hist *out) {
     return GM_OK;
 }
 
+// gm_verify over the nodes (verify_common.hpp): a node's score against its primitive() code or
+// the best of its children's scores, read through the CSR the solve left on the device.  A
+// node's key is its index, so no key or placement class exists here.
+__global__ __launch_bounds__(256) void graph_verify_kernel(const uint8_t *__restrict__ prim,
+                                                           const uint64_t *__restrict__ off,
+                                                           const uint32_t *__restrict__ kid,
+                                                           const uint16_t *__restrict__ score, uint64_t n, VerifyDev v) {
+    VerifyTally t;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+        const int p = prim[i];
+        uint32_t best = 0;
+        bool missing = false;
+        if (p == UNDECIDED)
+            for (uint64_t e = off[i]; e < off[i + 1]; e++) {
+                const uint32_t s = score[kid[e]];
+                t.n[6]++;
+                missing |= s == 0u;
+                best = max(best, s);
+            }
+        verify_note(v, t, verify_class(score[i], p, best, missing), i);
+    }
+    verify_flush(v, t);
+}
+
+static int graph_verify(Ctx *c, const VerifyDev &v) {
+    Graph *g = c->graph;
+    hipLaunchKernelGGL(graph_verify_kernel, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, g->prim, g->off, g->kid,
+                       g->score, g->n, v);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
+static int graph_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    Graph *g = c->graph;
+    if (words[0] >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const uint16_t s = score_of_record(rec);
+    GM_HIP(hipMemcpyAsync(g->score + words[0], &s, 2, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
 static void graph_free(Ctx *c) {
     Graph *g = c->graph;
     if (!g) return;
@@ -221,6 +263,6 @@ static void graph_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(graph_engine, GM_ENGINE_GRAPH, nullptr, graph_export,
-                 graph_query, graph_digest, graph_histogram, nullptr, graph_free)
+                 graph_query, graph_digest, graph_histogram, nullptr, graph_free, graph_verify, graph_poke)
 
 }  // namespace gm

@@ -8,6 +8,7 @@
 // per tier.  A launch-bound config: the table is 58 KB, far below any roofline.
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
+#include "verify_common.hpp"
 
 namespace gm {
 
@@ -147,6 +148,54 @@ static int small_dense_histogram(Ctx *c, Hist *out) {
     return GM_OK;
 }
 
+// gm_verify over the record table (verify_common.hpp): the reachable slots (record != 0xFFFF)
+// are the stored positions; slot = key, so no key or placement class exists here
+template <class D>
+__global__ __launch_bounds__(256) void small_verify_kernel(D d, const uint16_t *__restrict__ rec, VerifyDev v) {
+    VerifyTally t;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < D::SLOTS; i += gridDim.x * 256u) {
+        if (rec[i] == REC_UNSOLVED) continue;
+        const int p = d.primitive(i);
+        uint32_t best = 0;
+        bool missing = false;
+        if (p == UNDECIDED)
+            d.visit(i, [&](uint64_t ch) {
+                const int pc = d.primitive(ch);
+                uint32_t sc;
+                if (pc != UNDECIDED) {
+                    sc = score_of_primitive(pc);
+                } else {
+                    sc = score_of_record(rec[ch]);
+                    t.n[6]++;
+                    missing |= sc == 0u;
+                }
+                best = max(best, sc);
+                return true;
+            });
+        verify_note(v, t, verify_class(score_of_record(rec[i]), p, best, missing), (uint64_t)i);
+    }
+    verify_flush(v, t);
+}
+
+static int small_dense_verify(Ctx *c, const VerifyDev &v) {
+    SmallDense *s = c->sd;
+    hipLaunchKernelGGL(small_verify_kernel<DescTTT>, dim3(grid_counted(s->slots)), dim3(256), 0, c->stream, c->ttt,
+                       s->d_rec, v);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
+// the device table and the host copy gm_query answers from
+static int small_dense_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    SmallDense *s = c->sd;
+    const uint64_t k = words[0];
+    if (k >= s->slots || s->h_rec[k] == REC_UNSOLVED) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    s->h_rec[k] = rec;
+    GM_HIP(hipMemcpyAsync(s->d_rec + k, &s->h_rec[k], 2, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return GM_OK;
+}
+
 static void small_dense_free(Ctx *c) {
     SmallDense *s = c->sd;
     if (!s) return;
@@ -157,6 +206,7 @@ static void small_dense_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
-                 small_dense_query, small_dense_digest, small_dense_histogram, nullptr, small_dense_free)
+                 small_dense_query, small_dense_digest, small_dense_histogram, nullptr, small_dense_free,
+                 small_dense_verify, small_dense_poke)
 
 }  // namespace gm

@@ -844,6 +844,18 @@ static int sparse_histogram(Ctx *c, Hist *out) {
     });
 }
 
+static int sparse_verify(Ctx *c, const VerifyDev &v) {
+    return with_desc(c, [&](const auto &d) {
+        return tiers_verify(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, v);
+    });
+}
+
+static int sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+    return with_desc(c, [&](const auto &d) {
+        return tiers_poke(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, words[0], rec);
+    });
+}
+
 static void sparse_free(Ctx *c) {
     Sparse *sp = c->sp;
     if (!sp) return;
@@ -860,6 +872,6 @@ static void sparse_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
-                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free)
+                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free, sparse_verify, sparse_poke)
 
 }  // namespace gm

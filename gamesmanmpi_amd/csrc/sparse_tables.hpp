@@ -16,6 +16,7 @@
 // the per-edge LOOK_UP / primitive test of Process.lookup (src/new_process.py:102-133).
 #pragma once
 #include "sparse_common.hpp"
+#include "verify_common.hpp"
 
 namespace gm {
 
@@ -249,6 +250,30 @@ __device__ __forceinline__ int res_find(const WResRef &t, const K128 &key) {
     return -1;
 }
 
+// the slot a lookup of key ends at, or -1 when absent (gm_verify, gm_poke)
+__device__ __forceinline__ int64_t res_find_slot(const ResRef &t, uint64_t key) {
+    if (!t.s) return -1;
+    uint64_t h = home_slot(key, t.cap, t.loc);
+    for (uint64_t probe = 0; probe < t.cap; probe++) {
+        const uint64_t cur = t.s[h].key;
+        if (cur == key) return (int64_t)h;
+        if (cur == EMPTY_KEY) return -1;
+        h = h + 1 == t.cap ? 0 : h + 1;
+    }
+    return -1;
+}
+__device__ __forceinline__ int64_t res_find_slot(const WResRef &t, const K128 &key) {
+    if (!t.s) return -1;
+    uint64_t h = home_slot(key, t.cap, t.loc);
+    for (uint64_t probe = 0; probe < t.cap; probe++) {
+        const u64x2 v = *(const u64x2 *)&t.s[h];
+        if (v[0] == key.hi && v[1] == key.lo) return (int64_t)h;
+        if (v[0] == EMPTY_HI) return -1;
+        h = h + 1 == t.cap ? 0 : h + 1;
+    }
+    return -1;
+}
+
 // slot access shared by the two slot types
 __device__ __forceinline__ void slot_clear_key(uint64_t &k) { k = EMPTY_KEY; }
 __device__ __forceinline__ void slot_clear_key(K128 &k) { k = K128{0, EMPTY_HI}; }
@@ -451,6 +476,73 @@ __global__ void res_hist_kernel(D d, const typename KT<key_t<D>>::Slot *__restri
         score_bin_add(lds, bins, nbin, (uint16_t)slot_score(s[i]), w);
     }
     score_bins_flush(lds, bins, nbin);
+}
+
+// gm_verify over one tier table (verify_common.hpp): table `t` of group `g` of the G x ntabs
+// matrix `tabs` (row = owner rank, one row for the one-GPU engine; column = tier from the
+// root's, t_root).  Every occupied slot: its key (valid, its own representative, of this tier
+// and this owner), its place (a lookup ends at this slot), then its score against primitive()
+// or against the best of ALL its children -- made as retro_kernel makes them, looked up in
+// their owner's table of tiers t + 1 .. t + MAX_SKIP.
+template <class D>
+__global__ __launch_bounds__(256) void res_verify_kernel(D d, const typename KT<key_t<D>>::Res *__restrict__ tabs,
+                                                         int G, int ntabs, int g, int t, int64_t t_root, VerifyDev v) {
+    using K = key_t<D>;
+    constexpr int S = D::MAX_SKIP;
+    const typename KT<K>::Res self = tabs[(size_t)g * ntabs + t];
+    const auto plain = unreduced(d);
+    VerifyTally tally;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < self.cap; i += (uint64_t)gridDim.x * 256ull) {
+        const K k = slot_key(self.s[i]);
+        if (key_empty(k)) continue;
+        int cls;
+        if (!d.valid(k) || d.canon(k) != k || d.tier(k) - t_root != t || (int)owner_rank(k, (uint32_t)G) != g) {
+            cls = VF_BAD_KEY;
+        } else if (res_find_slot(self, k) != (int64_t)i) {
+            cls = VF_MISPLACED;
+        } else {
+            const uint32_t stored = (uint32_t)(slot_score(self.s[i]) & 0xFFFFu);
+            const int prim = d.primitive(k);
+            uint32_t best = 0;
+            bool missing = false;
+            if (prim == UNDECIDED) {
+                const int64_t tk = d.tier(k);
+                plain.visit(k, [&](const K &ch) {
+                    const int p = d.primitive(ch);
+                    uint32_t sc;
+                    if (p != UNDECIDED) {
+                        sc = score_of_primitive(p);
+                    } else {
+                        const int64_t dt = d.tier(ch) - tk;
+                        int f = -1;
+                        if (dt >= 1 && dt <= S && t + dt < ntabs) {
+                            const K cc = d.canon(ch);
+                            f = res_find(tabs[(size_t)owner_rank(cc, (uint32_t)G) * ntabs + (t + dt)], cc);
+                            tally.n[6]++;
+                        }
+                        missing |= f <= 0;
+                        sc = f > 0 ? (uint32_t)f : 0u;
+                    }
+                    best = max(best, sc);
+                    return true;
+                });
+            }
+            cls = verify_class(stored, prim, best, missing);
+        }
+        verify_note(v, tally, cls, k);
+    }
+    verify_flush(v, tally);
+}
+
+// gm_poke: the score of key's slot overwritten, or (remove) the slot emptied; *found = 1 if held
+template <class K>
+__global__ void res_poke_kernel(typename KT<K>::Res t, K key, uint64_t score, int remove, uint32_t *found) {
+    if (threadIdx.x || blockIdx.x) return;
+    const int64_t at = res_find_slot(t, key);
+    *found = at >= 0;
+    if (at < 0) return;
+    if (remove) slot_clear(t.s[at]);
+    else t.s[at].score = score;
 }
 
 template <class D>
@@ -684,6 +776,65 @@ inline int tiers_query(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>
         for (uint64_t i = 0; i < n; i++)
             if (part[i] != REC_UNSOLVED) recs[i] = part[i];
     }
+    return GM_OK;
+}
+
+// the groups x tiers matrix of table references on the device (a group without a tier: no table)
+template <class K>
+inline int tiers_matrix(Ctx *c, const std::vector<TierGroup<K>> &groups, DevBuf<typename KT<K>::Res> *tabs,
+                        int *ntabs) {
+    using Res = typename KT<K>::Res;
+    size_t nt = 0;
+    for (auto &g : groups) nt = std::max(nt, g.tiers->size());
+    std::vector<Res> h(std::max<size_t>(1, groups.size() * nt), Res{nullptr, 0, 0});
+    for (size_t g = 0; g < groups.size(); g++)
+        for (size_t t = 0; t < groups[g].tiers->size(); t++) h[g * nt + t] = res_ref_of((*groups[g].tiers)[t]);
+    GM_TRY(tabs->alloc(h.size()));
+    GM_HIP(hipMemcpyAsync(*tabs, h.data(), h.size() * sizeof(Res), hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));   // h leaves scope
+    *ntabs = (int)nt;
+    return GM_OK;
+}
+
+// gm_verify over tier tables: group g holds the keys of owner rank g (one group: the one-GPU engine)
+template <class D>
+inline int tiers_verify(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>> &groups, const VerifyDev &v) {
+    using K = key_t<D>;
+    DevBuf<typename KT<K>::Res> tabs;
+    int ntabs = 0;
+    GM_TRY(tiers_matrix<K>(c, groups, &tabs, &ntabs));
+    for (size_t g = 0; g < groups.size(); g++)
+        for (size_t t = 0; t < groups[g].tiers->size(); t++) {
+            const SpTierT<K> &T = (*groups[g].tiers)[t];
+            if (!T.slots || !T.cap) continue;
+            hipLaunchKernelGGL(res_verify_kernel<D>, dim3(grid_counted(T.cap)), dim3(256), 0, c->stream, d, tabs.p,
+                               (int)groups.size(), ntabs, (int)g, (int)t, groups[g].t_root, v);
+        }
+    GM_HIP(hipGetLastError());
+    GM_HIP(hipStreamSynchronize(c->stream));   // tabs leaves scope
+    return GM_OK;
+}
+
+// gm_poke in tier tables: the representative's slot in its owner's table of its tier
+template <class D>
+inline int tiers_poke(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>> &groups, const key_t<D> &key,
+                      uint16_t rec) {
+    using K = key_t<D>;
+    uint32_t found = 0;
+    if (d.valid(key)) {
+        const K k = d.canon(key);
+        const auto &g = groups[owner_rank(k, (uint32_t)groups.size())];
+        const int64_t t = d.tier(k) - g.t_root;
+        if (t >= 0 && t < (int64_t)g.tiers->size() && (*g.tiers)[t].slots) {
+            DevBuf<uint32_t> df;
+            GM_TRY(df.alloc(1));
+            hipLaunchKernelGGL(res_poke_kernel<K>, dim3(1), dim3(64), 0, c->stream, res_ref_of((*g.tiers)[t]), k,
+                               (uint64_t)score_of_record(rec), rec == REC_UNSOLVED ? 1 : 0, df.p);
+            GM_HIP(hipMemcpyAsync(&found, df, 4, hipMemcpyDeviceToHost, c->stream));
+            GM_HIP(hipStreamSynchronize(c->stream));
+        }
+    }
+    if (!found) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
     return GM_OK;
 }
 

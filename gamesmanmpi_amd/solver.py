@@ -25,6 +25,31 @@ def split_record(rec):
     return rec >> 14, rec & 0x3FFF
 
 
+def score_of_record(rec):
+    """The preference score of a child's record (csrc/gm_common.hpp): the mover prefers the
+    child with the largest -- a LOSS child over a TIE child over a WIN child, the shortest
+    LOSS or TIE, the longest WIN.  0 for 0xFFFF."""
+    rec = int(rec)
+    if rec == _lib.REC_UNSOLVED:
+        return 0
+    v, r = rec >> 14, rec & 0x3FFF
+    if v == WIN:
+        return 0x4000 | r
+    return (0x8000 if v == TIE else 0xC000) | (0x3FFF - r)
+
+
+def best_move(records):
+    """Index of the child the solver would play among `records` (the first of equals), and the
+    parent's (value, remoteness) that choice gives; (None, None) without children."""
+    if not len(records):
+        return None, None
+    best = max(range(len(records)), key=lambda i: score_of_record(records[i]))
+    v, r = split_record(records[best])
+    if v is None:
+        return best, (None, None)
+    return best, ({LOSS: WIN, TIE: TIE, WIN: LOSS}[v], r + 1)
+
+
 class NoDescriptor(RuntimeError):
     pass
 
@@ -131,6 +156,46 @@ class Context:
         _lib.check(self.L.gm_histogram(self.h, out.ctypes.data if out.size else None, n_rem.value,
                                        ctypes.byref(n_rem), ctypes.byref(n)))
         return out
+
+    def verify(self, cap=64):
+        """gm_verify: the held table checked against the game rules on the device.  Returns
+        (dict of gm_verify_t plus n_bad, up to `cap` offending keys as Python ints, ascending)."""
+        out = _lib.Verify()
+        n_bad = ctypes.c_uint64()
+        keys = np.zeros((max(1, cap), self.words), dtype=np.uint64)
+        _lib.check(self.L.gm_verify(self.h, ctypes.byref(out), keys.ctypes.data if cap else None, cap,
+                                    ctypes.byref(n_bad)))
+        n = min(cap, n_bad.value)
+        return out.as_dict(), [_lib.words_to_int(keys[i]) for i in range(n)]
+
+    def poke(self, key, record):
+        """gm_poke (test hook): overwrite one held position's record; 0xFFFF removes it."""
+        w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
+        _lib.check(self.L.gm_poke(self.h, w, int(record)))
+
+    def expand(self, key):
+        """gm_expand_host: (primitive code, children in the plugin's gen_moves order, tier)."""
+        n, p, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        kids = (ctypes.c_uint64 * (64 * self.words))()
+        if self.words > 1:
+            w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
+            _lib.check(self.L.gm_expand_host_key(self.h, w, kids, 64, ctypes.byref(n), ctypes.byref(p),
+                                                 ctypes.byref(t)))
+        else:
+            _lib.check(self.L.gm_expand_host(self.h, int(key), kids, 64, ctypes.byref(n), ctypes.byref(p),
+                                             ctypes.byref(t)))
+        W = self.words
+        return p.value, [_lib.words_to_int(kids[W * i:W * i + W]) for i in range(n.value)], t.value
+
+    def moves(self, key):
+        """What the mover can do at `key`: (children in the plugin's gen_moves order, their
+        records, the index of the child the solver would play); a primitive position has no
+        moves and index None."""
+        prim, kids, _ = self.expand(key)
+        if prim != UNDECIDED or not kids:
+            return [], np.zeros(0, dtype=np.uint16), None
+        recs = self.query(kids)
+        return kids, recs, best_move(recs)[0]
 
     def stats(self):
         s = _lib.Stats()
@@ -257,6 +322,30 @@ class Solver:
             keys, recs = self.ctx.export()
             return analysis.from_records(recs, [len(self.codec.members(k)) for k in keys])
         return self.ctx.histogram()
+
+    def verify(self, cap=64):
+        """Check the solved table against the game rules on the device (gm_verify):
+        (counts dict, up to `cap` offending keys)."""
+        return self.ctx.verify(cap)
+
+    def moves(self, pos):
+        """The moves at `pos` and what each is worth: rows (move, child position, value,
+        remoteness) in the plugin's gen_moves order, and the row the solver would play (None at
+        a primitive position)."""
+        if self.module.primitive(pos) != UNDECIDED:
+            return [], None
+        labels = list(self.module.gen_moves(pos))
+        if self.codec.game_id == _lib.GAME_GRAPH:
+            # no device descriptor: the plugin's own moves, looked up by position
+            kids = [self.codec.key(self.module.do_move(pos, m)) for m in labels]
+            recs = self.ctx.query(kids)
+            best = best_move(recs)[0]
+        else:
+            kids, recs, best = self.ctx.moves(self.codec.key(pos))
+            if len(labels) != len(kids):   # a plugin that lists a move twice: number the children
+                labels = list(range(len(kids)))
+        rows = [(m, self.codec.pos(k)) + split_record(r) for m, k, r in zip(labels, kids, recs)]
+        return rows, (rows[best] if best is not None else None)
 
     def close(self):
         self.ctx.close()

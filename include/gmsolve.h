@@ -320,6 +320,47 @@ int gm_digest(gm_ctx *ctx, uint64_t *digest, uint64_t *n);
  * -sd/--statsdir stores the raw tables only (src/new_process.py:76-78). */
 int gm_histogram(gm_ctx *ctx, uint64_t *counts, int cap, int *n_rem, uint64_t *n);
 
+/* The result of gm_verify.  A position counts in exactly one class: the first that applies, in
+ * the order of the fields. */
+typedef struct {
+    uint64_t checked;        /* stored positions examined */
+    uint64_t bad_key;        /* stored key that is not valid(), not its own canon(), or sits in the wrong tier's table */
+    uint64_t misplaced;      /* sparse tables: a lookup of the stored key does not end at its own slot (duplicate / broken chain) */
+    uint64_t bad_primitive;  /* primitive position whose record is not (primitive value, remoteness 0) */
+    uint64_t missing_child;  /* interior position with at least one child absent from the table */
+    uint64_t bad_value;      /* interior position, all children present, record != reduction of their records */
+    uint64_t child_lookups;  /* child records read */
+    int32_t  root_ok;        /* 1: the root is stored and its record equals gm_solve's root record */
+    int32_t  reserved;
+} gm_verify_t;
+
+/* Check the table of the last solve against the game rules, on the device: the records gm_query
+ * would return, over exactly the stored positions (one representative per symmetry orbit, so
+ * checked == gm_stats_t.n_stored; the root's region for the dense engines; the n nodes of a
+ * graph).  For an acyclic game the table is the solution iff the root is in it, every stored
+ * primitive position carries (primitive value, 0), and every stored interior position has all
+ * its children stored and the reduction of their records as its own; children are generated as
+ * the backward pass generates them, every one of them is visited, and a primitive child is
+ * answered by primitive() without a lookup.  A pass does not rule out extra positions that the
+ * root cannot reach.
+ * *n_bad = the sum of the five classes.  Up to cap offending keys are written to bad_key_words,
+ * gm_key_words() words each, ascending: all of them when *n_bad <= cap, else any cap of them.
+ * bad_key_words == NULL or cap == 0: counts only.  Nothing else leaves the device.
+ * Returns GM_OK whenever the check ran, whatever it found.  GM_E_STATE before a solve, after a
+ * failed one, and in a multi-process solve (a rank does not hold the tables of its children's
+ * owners; virtual ranks are checked as one table).  GM_E_ARG for out == NULL.
+ * The reference has no counterpart: the only consistency evidence of a run is its root line
+ * (src/new_process.py:42-53); this replaces comparing a table with a second solve. */
+int gm_verify(gm_ctx *ctx, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap, uint64_t *n_bad);
+
+/* Test hook (in the spirit of GM_OPT_POISON): overwrite the stored record of one held position
+ * -- the copy gm_query reads; under a symmetry reduction the representative's slot.  Record
+ * 0xFFFF removes the position (a sparse slot is emptied, a dense code or graph score becomes
+ * 0).  GM_E_KEY if the key is not held, GM_E_ARG for a record the table cannot express,
+ * GM_E_STATE before a solve or in a multi-process solve.  Drops a kept histogram; the next
+ * solve rewrites every table. */
+int gm_poke(gm_ctx *ctx, const uint64_t *key_words, uint16_t record);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
-    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis]
+    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -10,7 +10,9 @@ are strings while plugins return src.utils ints (:6), and its TIE
 branch tests LOSS twice (:34).  This drop-in prints the message the reference
 intends for the root's canonical value, computed on the GPU by libgmsolve.so;
 ``--remoteness`` adds the launcher's "<V> in <R> moves" line, ``--analysis`` the table of
-positions by value and remoteness (gamesmanmpi_amd/analysis.py).
+positions by value and remoteness (gamesmanmpi_amd/analysis.py), ``--verify`` the check of the
+solved table against the game rules (gm_verify, gamesmanmpi_amd/verify.py: one line, then any
+offending positions; the exit status is non-zero when the table is inconsistent).
 """
 import argparse
 import os
@@ -34,6 +36,7 @@ def main(argv=None):
     p.add_argument("--heaps", type=int)
     p.add_argument("--remoteness", action="store_true")
     p.add_argument("--analysis", action="store_true")
+    p.add_argument("--verify", action="store_true")
     p.add_argument("--device", type=int, default=-1)
     args = p.parse_args(argv)
     args.engine = "auto"
@@ -47,8 +50,12 @@ def main(argv=None):
     if args.analysis:
         from gamesmanmpi_amd import analysis
         print(analysis.format_table(s.analysis()))
+    status = 0
+    if args.verify:
+        from gamesmanmpi_amd import verify
+        status = 0 if verify.report(s, sys.stdout) else 1
     s.close()
-    return 0
+    return status
 
 
 if __name__ == "__main__":

@@ -31,7 +31,14 @@ Differences, on purpose:
   patches the subtraction plugin, ``--engine``, ``--device``, ``--stats``;
 * ``--analysis`` prints, after the root line, the whole solve's positions by value and
   remoteness (gm_histogram, gamesmanmpi_amd/analysis.py); with ``-sd DIR`` rank 0 also
-  writes them to ``DIR/stats/analysis.json``.
+  writes them to ``DIR/stats/analysis.json``;
+* ``--verify`` checks the solved table against the game rules on the device (gm_verify,
+  gamesmanmpi_amd/verify.py) and prints ``Verified N positions: consistent`` -- or the
+  counts by class and up to 16 offending positions with their moves -- after the root line;
+  the exit status is non-zero when anything is inconsistent, and with ``-sd DIR`` rank 0
+  writes ``DIR/stats/verify.json``.  Ranks that share one solve on rank 0 verify as one
+  process does; a solve sharded over processes is refused before it starts, since no rank
+  holds the tables of its children's owners.
 """
 import argparse
 import cProfile
@@ -67,6 +74,8 @@ def build_parser():
     p.add_argument("--stats", action="store_true", help="print solve statistics (JSON) to stderr")
     p.add_argument("--analysis", action="store_true",
                    help="after the root line, print the positions by value and remoteness")
+    p.add_argument("--verify", action="store_true",
+                   help="after the root line, check the solved table against the game rules on the device")
     p.add_argument("--sd-format", choices=("auto", "npz", "reference", "both"), default="auto",
                    help="-sd output: npz table, the reference's shelve layout, or both (auto: both up to "
                         "%d positions, else npz)" % SHELVE_AUTO_LIMIT)
@@ -164,6 +173,12 @@ def run(args, out=sys.stdout):
         plan = dist.broadcast(rank_plan(world, int(os.environ.get("LOCAL_WORLD_SIZE", world)),
                                         _lib.lib().gm_device_count()) if rank == 0 else None)
         logging.debug("rank %d of %d: %s", rank, world, plan)
+        if plan == "sharded" and getattr(args, "verify", False):
+            if rank == 0:
+                print("--verify needs the whole table in one process: this solve is sharded over %d processes, and "
+                      "a rank does not hold the tables of its children's owners.  Run it on one process (virtual "
+                      "ranks included)." % world, file=sys.stderr)
+            return 2
         if plan == "single" and rank != 0:
             # rank 0 solves for every rank and prints the root line; wait for it by polling
             # the group's store (a barrier would time out under a solve longer than the
@@ -202,6 +217,10 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
         out.flush()
     if getattr(args, "analysis", False):
         report_analysis(args, solver, rank, world, plan, out)
+    status = 0
+    if getattr(args, "verify", False) and rank == 0:
+        from gamesmanmpi_amd import verify
+        status = 0 if verify.report(solver, out, args.statsdir) else 1
     if args.stats:
         st = solver.ctx.stats()
         st["rank"] = rank
@@ -211,7 +230,7 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     solver.close()
     if plan == "single":
         dist.release_waiters(world)
-    return 0
+    return status
 
 
 def report_analysis(args, solver, rank, world, plan, out):
