@@ -27,6 +27,8 @@ OPT_BOX_SPLIT = 16
 OPT_BOX_TRANSPORT = 17
 OPT_SPARSE_TRANSPORT = 18
 OPT_POISON = 19
+OPT_LOOPY = 20
+REC_DRAW = 0xC000   # (DRAW, 0): the table of a loopy graph solve only
 ABI_VERSION = 2
 BUF_DENSE_TABLE = 1
 PLAN_SHAPE, PLAN_OWN, PLAN_FILL, PLAN_SEND, PLAN_RECV, PLAN_OPS, PLAN_XDEST = 0, 1, 2, 3, 4, 5, 6
@@ -49,7 +51,7 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
-           "gm_histogram", "gm_verify", "gm_poke")
+           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count")
 
 
 class GMError(RuntimeError):
@@ -139,6 +141,7 @@ def lib():
         "gm_histogram": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int), P(u64)]),
         "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
         "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
+        "gm_draw_count": (ctypes.c_int, [vp, P(u64)]),
         "gm_stats": (ctypes.c_int, [vp, P(Stats)]),
         "gm_tier_counts": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int)]),
         "gm_adopt_buffer": (ctypes.c_int, [vp, ctypes.c_int, vp, u64]),

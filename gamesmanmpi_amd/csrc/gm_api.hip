@@ -296,6 +296,11 @@ int gm_set_option(gm_ctx *h, int opt, int64_t v) {
         if (v < 1 || v > 64) { set_error("virtual ranks must be 1..64"); return GM_E_ARG; }
         c->virtual_ranks = (int)v;
         return GM_OK;
+    case GM_OPT_LOOPY:
+        if (c->game != GM_GAME_GRAPH) { set_error("GM_OPT_LOOPY is the graph engine's: a GM_GAME_GRAPH context"); return GM_E_ARG; }
+        if (v < 0 || v > 1) { set_error("loopy must be 0 or 1"); return GM_E_ARG; }
+        c->loopy = (int)v;
+        return GM_OK;
     }
     set_error("unknown option %d", opt);
     return GM_E_ARG;
@@ -405,6 +410,7 @@ int gm_solve(gm_ctx *h, uint64_t root, uint64_t *n_positions, uint16_t *root_rec
     c->solved = false;
     c->solved_by = nullptr;
     c->hist_is_kept = false;
+    c->n_draw = 0;
     int32_t launches = c->stats.kernel_launches;
     c->stats = gm_stats_t{};
     c->stats.kernel_launches = c->timing ? launches : 0;
@@ -516,6 +522,7 @@ int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16
     c->solved = false;
     c->solved_by = nullptr;
     c->hist_is_kept = false;
+    c->n_draw = 0;
     c->stats = gm_stats_t{};
     if (c->world > 1 && c->virtual_ranks > 1) {
         set_error("virtual ranks and a multi-process communicator are exclusive");
@@ -597,6 +604,7 @@ int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *o
     c->solved = false;
     c->solved_by = nullptr;
     c->hist_is_kept = false;
+    c->n_draw = 0;
     if (!prim || !off) { set_error("gm_solve_graph needs primitive and child_off"); return GM_E_ARG; }
     if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
     if (n >= (1ull << 32)) { set_error("graphs are limited to 2^32 - 1 positions"); return GM_E_ARG; }
@@ -653,6 +661,7 @@ int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) 
     if (counts && c->hist_is_kept) {
         // the census of the counts == NULL query just before: one pass over the table per pair
         for (int v = 0; v < 3; v++) H.v[v].swap(c->hist_kept[v]);
+        H.other = c->hist_kept_other;
     } else {
         GM_TRY(c->solved_by->histogram(c, &H));
     }
@@ -662,6 +671,7 @@ int gm_histogram(gm_ctx *h, uint64_t *counts, int cap, int *n_rem, uint64_t *n) 
     *n = H.total();
     if (!counts) {
         for (int v = 0; v < 3; v++) c->hist_kept[v].swap(H.v[v]);
+        c->hist_kept_other = H.other;
         c->hist_is_kept = true;
         return GM_OK;
     }
@@ -738,12 +748,21 @@ int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap
 int gm_poke(gm_ctx *h, const uint64_t *key_words, uint16_t record) {
     GM_TRY(need_solved(h));
     if (!key_words) { set_error("key_words is NULL"); return GM_E_ARG; }
-    if (record != REC_UNSOLVED && (record >> 14) > TIE) { set_error("gm_poke: not a record"); return GM_E_ARG; }
     Ctx *c = &h->c;
+    // (DRAW, 0) is a record of the graph engine's loopy tables only (graph_poke refuses it on the others)
+    const bool draw = record == 0xC000 && c->solved_by == &graph_engine;
+    if (record != REC_UNSOLVED && (record >> 14) > TIE && !draw) { set_error("gm_poke: not a record"); return GM_E_ARG; }
     GM_TRY(need_whole_table(c, "gm_poke"));
     GM_HIP(hipSetDevice(c->device));
     c->hist_is_kept = false;
     return c->solved_by->poke(c, key_words, record);
+}
+
+int gm_draw_count(gm_ctx *h, uint64_t *n_draw) {
+    GM_TRY(need_solved(h));
+    if (!n_draw) { set_error("n_draw is NULL"); return GM_E_ARG; }
+    *n_draw = h->c.n_draw;
+    return GM_OK;
 }
 
 int gm_stats(gm_ctx *h, gm_stats_t *out) {

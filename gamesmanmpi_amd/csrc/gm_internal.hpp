@@ -110,6 +110,7 @@ struct Ctx {
     int box_flow_fallbacks = 0;     // dataflow solves of this context that fell back to tier launches
     int box_split = 0;       // split box engine (N > 1): 0 halves, 1 comparisons (GM_OPT_BOX_SPLIT)
     int symmetry = 1;        // sparse engines: store one representative per symmetry orbit (games.hpp)
+    int loopy = 0;           // graph engine: 1 = the loopy solve, cycles and DRAW allowed (GM_OPT_LOOPY)
 
     // results
     bool solved = false;
@@ -118,10 +119,12 @@ struct Ctx {
     K128 root_wide{0, 0};    // a wide context's root (gm_solve_key), for gm_verify's root check
     uint64_t n_positions = 0;
     uint16_t root_record = REC_UNSOLVED;
+    uint64_t n_draw = 0;     // DRAW positions of the last solve (gm_draw_count): a loopy graph solve's, else 0
     gm_stats_t stats{};
     std::vector<uint64_t> tier_counts;
     // gm_histogram: the census a counts == NULL query computed, kept for the fill call that follows
     std::vector<uint64_t> hist_kept[3];
+    uint64_t hist_kept_other = 0;
     bool hist_is_kept = false;
 
     // device buffer cache (dev_alloc / dev_free)
@@ -164,7 +167,7 @@ struct Engine {
 #else
 #define GM_ENGINE_RECORD(name, ...) const Engine name = {__VA_ARGS__};
 #endif
-extern const Engine graph_engine;         // graph.hip
+extern const Engine graph_engine;         // graph.hip, graph_loopy.hip
 extern const Engine small_dense_engine;   // small_dense.hip
 extern const Engine dense_sub_engine;     // dense_sub.hip: the block engine
 extern const Engine dense_box_engine;     // dense_box.hip: the box-tiled engine for 8 heaps

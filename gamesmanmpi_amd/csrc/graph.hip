@@ -12,23 +12,16 @@
 // remain means a cycle (the reference would never terminate either) and fails.
 // Rounds = the height of the graph; a position is written once, when final, so
 // reading a child in the round it is written is benign.
-#include "gm_internal.hpp"
+//
+// GM_OPT_LOOPY 1 solves with graph_loopy.hip instead (cycles, DRAW); the table it leaves is read
+// by the kernels below, which know the DRAW score (graph_common.hpp) and its rule in gm_verify.
+#include "graph_common.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
 
 #include <algorithm>
 
 namespace gm {
-
-struct Graph {
-    uint64_t n = 0;
-    uint8_t *prim = nullptr;
-    uint64_t *off = nullptr;
-    uint32_t *kid = nullptr;
-    uint16_t *score = nullptr;
-    unsigned long long *d_count = nullptr;
-    uint32_t *d_err = nullptr;
-};
 
 __global__ __launch_bounds__(256) void graph_init_kernel(const uint8_t *__restrict__ prim, uint64_t n,
                                                          uint16_t *__restrict__ score, uint32_t *err) {
@@ -70,31 +63,32 @@ __global__ void graph_records_kernel(const uint16_t *__restrict__ score, const u
     uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t k = idx ? idx[i] : i;
-    out[i] = k < total ? record_of_score(score[k]) : REC_UNSOLVED;
+    out[i] = k < total ? graph_record(score[k]) : REC_UNSOLVED;
 }
 
 __global__ void graph_digest_kernel(const uint16_t *__restrict__ score, uint64_t n, unsigned long long *acc) {
     uint64_t sum = 0;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        sum += digest_term(i, record_of_score(score[i]));
+        sum += digest_term(i, graph_record(score[i]));
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     if ((threadIdx.x & 63) == 0) atomicAdd(acc, (unsigned long long)sum);
 }
 
-// census of the nodes' scores (hist_common.hpp score bins: LDS, or global for deep graphs)
+// census of the nodes' scores (hist_common.hpp score bins: LDS, or global for deep graphs); the
+// DRAW nodes of a loopy table have no row and are left out (Hist::other counts them)
 __global__ void graph_hist_kernel(const uint16_t *__restrict__ score, uint64_t n, unsigned long long *bins,
-                                  uint32_t nbin, int use_lds) {
+                                  uint32_t nbin, int use_lds, int loopy) {
     uint32_t *lds = score_bins_open(nbin, use_lds);
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        score_bin_add(lds, bins, nbin, score[i], 1u);
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint16_t s = score[i];
+        if (loopy && s == SCORE_DRAW) continue;
+        score_bin_add(lds, bins, nbin, s, 1u);
+    }
     score_bins_flush(lds, bins, nbin);
 }
 
-static unsigned grid_of(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
-
-static void graph_free(Ctx *c);
-
-int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid) {
+// the graph on the device and an empty score table, for either solve
+int graph_upload(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid) {
     graph_free(c);
     if (!n) { set_error("empty graph"); return GM_E_ARG; }
     Graph *g = c->graph = new Graph();
@@ -102,17 +96,26 @@ int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, co
     const uint64_t m = off[n];
     for (uint64_t i = 0; i < m; i++)
         if (kid[i] >= n) { set_error("child index %u out of range", kid[i]); return GM_E_ARG; }
-    double t0 = now_ms();
+    g->t0 = now_ms();
     GM_TRY(dev_alloc(c, (void **)&g->prim, n));
     GM_TRY(dev_alloc(c, (void **)&g->off, (n + 1) * 8));
     GM_TRY(dev_alloc(c, (void **)&g->kid, std::max<uint64_t>(m, 1) * 4));
-    GM_TRY(dev_alloc(c, (void **)&g->score, n * 2));
+    GM_TRY(dev_alloc(c, (void **)&g->score, (n + 1) / 2 * 4));   // whole words: the loopy solve's atomics are 32-bit
     GM_TRY(dev_alloc(c, (void **)&g->d_count, 8));
     GM_TRY(dev_alloc(c, (void **)&g->d_err, 4));
     GM_HIP(hipMemcpyAsync(g->prim, prim, n, hipMemcpyHostToDevice, c->stream));
     GM_HIP(hipMemcpyAsync(g->off, off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     if (m) GM_HIP(hipMemcpyAsync(g->kid, kid, m * 4, hipMemcpyHostToDevice, c->stream));
     GM_HIP(hipMemsetAsync(g->d_err, 0, 4, c->stream));
+    return GM_OK;
+}
+
+int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid) {
+    if (c->loopy) return graph_solve_loopy(c, n, prim, off, kid);
+    GM_TRY(graph_upload(c, n, prim, off, kid));
+    Graph *g = c->graph;
+    const double t0 = g->t0;
+    const uint64_t m = off[n];
     hipLaunchKernelGGL(graph_init_kernel, dim3(grid_of(n)), dim3(256), 0, c->stream, g->prim, n, g->score, g->d_err);
     uint64_t interior = 0;
     for (uint64_t i = 0; i < n; i++) interior += prim[i] == UNDECIDED;
@@ -202,17 +205,33 @@ static int graph_histogram(Ctx *c, Hist *out) {
         ScoreBins b;
         GM_TRY(score_bins_begin(c, nbin, &b));
         hipLaunchKernelGGL(graph_hist_kernel, dim3(std::min(grid_of(g->n), 2048u)), dim3(256), b.lds_bytes, c->stream,
-                           g->score, g->n, b.d, b.nbin, b.use_lds);
+                           g->score, g->n, b.d, b.nbin, b.use_lds, (int)g->loopy);
         bool deeper = false;
         GM_TRY(score_bins_end(c, &b, out, nbin < full ? &deeper : nullptr));
         if (!deeper) break;
     }
+    // every node of a loopy table has a score, so what has no row is DRAW
+    if (g->loopy) out->other = g->n - out->total();
     return GM_OK;
 }
 
 // gm_verify over the nodes (verify_common.hpp): a node's score against its primitive() code or
 // the best of its children's scores, read through the CSR the solve left on the device.  A
 // node's key is its index, so no key or placement class exists here.
+//
+// LOOPY: the rule of a loopy table (graph_common.hpp).  A primitive carries its value's score,
+// DRAW included; an interior node the loopy reduction of its children -- the best child under
+// LOSS > TIE > DRAW > WIN, a DRAW best child making the parent DRAW.  That local rule is also
+// sufficient: a W/L/T label with finite remoteness is sound by induction on the remoteness
+// (its witness chain strictly descends to a primitive), every truly decided node is then
+// forced to its label by induction on its true remoteness, and what remains is DRAW.
+GM_HD int verify_class_loopy(uint32_t stored, int prim, uint32_t best_key, bool missing) {
+    if (prim != UNDECIDED) return stored == (prim == DRAW ? SCORE_DRAW : score_of_primitive(prim)) ? VF_OK : VF_BAD_PRIMITIVE;
+    if (missing) return VF_MISSING_CHILD;
+    return stored == loopy_parent_score(best_key) ? VF_OK : VF_BAD_VALUE;
+}
+
+template <bool LOOPY>
 __global__ __launch_bounds__(256) void graph_verify_kernel(const uint8_t *__restrict__ prim,
                                                            const uint64_t *__restrict__ off,
                                                            const uint32_t *__restrict__ kid,
@@ -227,17 +246,22 @@ __global__ __launch_bounds__(256) void graph_verify_kernel(const uint8_t *__rest
                 const uint32_t s = score[kid[e]];
                 t.n[6]++;
                 missing |= s == 0u;
-                best = max(best, s);
+                best = max(best, LOOPY ? loopy_key(s) : s);
             }
-        verify_note(v, t, verify_class(score[i], p, best, missing), i);
+        verify_note(v, t, LOOPY ? verify_class_loopy(score[i], p, best, missing) : verify_class(score[i], p, best, missing),
+                    i);
     }
     verify_flush(v, t);
 }
 
 static int graph_verify(Ctx *c, const VerifyDev &v) {
     Graph *g = c->graph;
-    hipLaunchKernelGGL(graph_verify_kernel, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, g->prim, g->off, g->kid,
-                       g->score, g->n, v);
+    if (g->loopy)
+        hipLaunchKernelGGL(graph_verify_kernel<true>, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, g->prim, g->off,
+                           g->kid, g->score, g->n, v);
+    else
+        hipLaunchKernelGGL(graph_verify_kernel<false>, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, g->prim, g->off,
+                           g->kid, g->score, g->n, v);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
@@ -245,13 +269,14 @@ static int graph_verify(Ctx *c, const VerifyDev &v) {
 static int graph_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     Graph *g = c->graph;
     if (words[0] >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-    const uint16_t s = score_of_record(rec);
+    if (rec == REC_DRAW && !g->loopy) { set_error("gm_poke: not a record"); return GM_E_ARG; }
+    const uint16_t s = graph_score(rec);
     GM_HIP(hipMemcpyAsync(g->score + words[0], &s, 2, hipMemcpyHostToDevice, c->stream));
     GM_HIP(hipStreamSynchronize(c->stream));
     return GM_OK;
 }
 
-static void graph_free(Ctx *c) {
+void graph_free(Ctx *c) {
     Graph *g = c->graph;
     if (!g) return;
     for (void *p : {(void *)g->prim, (void *)g->off, (void *)g->kid, (void *)g->score, (void *)g->d_count,

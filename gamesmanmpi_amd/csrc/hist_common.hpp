@@ -31,15 +31,16 @@ namespace gm {
 // counts[value][remoteness], grown on demand
 struct Hist {
     std::vector<uint64_t> v[3];
+    uint64_t other = 0;   // positions counted that have no row: the DRAW nodes of a loopy graph table
     void add(int value, uint32_t rem, uint64_t n) {
         if (!n) return;
         if (v[value].size() <= rem) v[value].resize(rem + 1, 0);
         v[value][rem] += n;
     }
-    void clear() { for (auto &x : v) x.clear(); }
+    void clear() { for (auto &x : v) x.clear(); other = 0; }
     uint32_t n_rem() const { return (uint32_t)std::max({v[0].size(), v[1].size(), v[2].size()}); }
     uint64_t total() const {
-        uint64_t s = 0;
+        uint64_t s = other;
         for (auto &x : v)
             for (uint64_t k : x) s += k;
         return s;

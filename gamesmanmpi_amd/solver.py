@@ -38,15 +38,24 @@ def score_of_record(rec):
     return (0x8000 if v == TIE else 0xC000) | (0x3FFF - r)
 
 
+def move_rank(rec):
+    """score_of_record with the DRAW children of a loopy solve in their place: LOSS > TIE >
+    DRAW > WIN (csrc/graph_common.hpp loopy_key).  Without a DRAW record the order is
+    score_of_record's."""
+    return 0xFFFF if int(rec) == _lib.REC_DRAW else 2 * score_of_record(rec)
+
+
 def best_move(records):
     """Index of the child the solver would play among `records` (the first of equals), and the
     parent's (value, remoteness) that choice gives; (None, None) without children."""
     if not len(records):
         return None, None
-    best = max(range(len(records)), key=lambda i: score_of_record(records[i]))
+    best = max(range(len(records)), key=lambda i: move_rank(records[i]))
     v, r = split_record(records[best])
     if v is None:
         return best, (None, None)
+    if v == DRAW:
+        return best, (DRAW, 0)
     return best, ({LOSS: WIN, TIE: TIE, WIN: LOSS}[v], r + 1)
 
 
@@ -141,6 +150,12 @@ class Context:
         else:
             _lib.check(self.L.gm_query(self.h, keys.ctypes.data, out.ctypes.data, len(keys)))
         return out
+
+    def draw_count(self):
+        """gm_draw_count: the DRAW positions of the last solve (0 unless it was a loopy graph solve)."""
+        n = ctypes.c_uint64()
+        _lib.check(self.L.gm_draw_count(self.h, ctypes.byref(n)))
+        return n.value
 
     def digest(self):
         d, n = ctypes.c_uint64(), ctypes.c_uint64()
@@ -258,12 +273,19 @@ class Solver:
     A plugin that no device descriptor reproduces is solved as an explicit graph
     (gamesmanmpi_amd/graph.py): the host enumerates it with the plugin's own
     functions and the device resolves it; ``graph=True`` forces that path,
-    ``graph=False`` raises NoDescriptor instead.
+    ``graph=False`` raises NoDescriptor instead.  ``loopy=True`` is for games in which a
+    position can repeat: it takes the graph path whatever the plugin is and solves with
+    GM_OPT_LOOPY, so that cycles are allowed and a position neither side can decide is DRAW.
     """
 
-    def __init__(self, module, root=None, device=-1, engine=None, codec=None, graph=None):
+    def __init__(self, module, root=None, device=-1, engine=None, codec=None, graph=None, loopy=False):
         self.module = module
         self.root = module.initial_position() if root is None else root
+        self.loopy = bool(loopy)
+        if self.loopy:
+            if graph is False or (codec is not None and codec.game_id != _lib.GAME_GRAPH):
+                raise ValueError("a loopy solve is an explicit-graph solve")
+            graph = True
         if codec is None and not graph:
             codec = games.identify(module, self.root)
         if codec is None:
@@ -278,6 +300,8 @@ class Solver:
         self.ctx = Context(self.codec.game_id, self.codec.params, device)
         if engine is not None:
             self.ctx.set_option(_lib.OPT_ENGINE, engine)
+        if self.loopy:
+            self.ctx.set_option(_lib.OPT_LOOPY, 1)
         self.root_key = self.codec.key(self.root)
         self.n_positions = None
         self.root_record = None
@@ -302,6 +326,8 @@ class Solver:
     def root_line(self):
         """The reference's root line (src/new_process.py:47-52)."""
         v, r = split_record(self.root_record)
+        if v == DRAW:   # nobody can force an end: a move count has no meaning
+            return to_str(v)
         return "%s in %d moves" % (to_str(v), r)
 
     def lookup(self, pos):
@@ -320,8 +346,17 @@ class Solver:
         if self.codec.game_id == _lib.GAME_GRAPH and self.codec.gens:
             from . import analysis
             keys, recs = self.ctx.export()
-            return analysis.from_records(recs, [len(self.codec.members(k)) for k in keys])
+            keep = recs != _lib.REC_DRAW   # DRAW has no row (draw_count)
+            return analysis.from_records(recs[keep], [len(self.codec.members(k)) for k in keys[keep]])
         return self.ctx.histogram()
+
+    def draw_count(self):
+        """DRAW positions of the solve (0 unless it was loopy); orbit representatives are
+        weighted by orbit size, as in analysis()."""
+        if self.codec.game_id == _lib.GAME_GRAPH and self.codec.gens:
+            keys, recs = self.ctx.export()
+            return sum(len(self.codec.members(k)) for k in keys[recs == _lib.REC_DRAW])
+        return self.ctx.draw_count()
 
     def verify(self, cap=64):
         """Check the solved table against the game rules on the device (gm_verify):

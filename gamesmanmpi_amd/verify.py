@@ -29,6 +29,8 @@ def summary_line(res):
 
 
 def _record_text(value, remoteness):
+    if value == 3:   # DRAW: no end to count moves to
+        return to_str(value)
     return "not stored" if value is None else "%s in %d" % (to_str(value), remoteness)
 
 

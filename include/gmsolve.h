@@ -19,6 +19,8 @@
  *
  * Records (u16): bits 15..14 = value (0 WIN, 1 LOSS, 2 TIE; the codes of
  * reference src/utils.py:4), bits 13..0 = remoteness.  0xFFFF = not reached.
+ * 0xC000 (value 3 = DRAW, remoteness 0) appears only in the table of a loopy graph
+ * solve (GM_OPT_LOOPY): a position from which neither side can force an end.
  */
 #ifndef GMSOLVE_H
 #define GMSOLVE_H
@@ -57,7 +59,8 @@ enum {
     GM_E_HIP = -3,          /* HIP runtime error (no device, launch failure, ...) */
     GM_E_NOMEM = -4,        /* device or host allocation failed */
     GM_E_STATE = -5,        /* call out of order (e.g. export before solve) */
-    GM_E_DRAW = -6,         /* a DRAW primitive was reached (unsupported) */
+    GM_E_DRAW = -6,         /* a DRAW primitive was reached: unsupported by every engine but
+                               the graph engine's loopy mode (GM_OPT_LOOPY), which keeps it as (DRAW, 0) */
     GM_E_NOMOVES = -7,      /* non-primitive position without moves (the reference hangs) */
     GM_E_CAP = -8,          /* caller buffer too small / remoteness overflow */
     GM_E_COMM = -9,         /* RCCL failure */
@@ -150,7 +153,7 @@ enum {
                                a rank that fails marks the segment and its peers fail at once).  1 runs
                                when the ranks share one GPU (RCCL refuses that); all the ranks of one
                                node.  Set on every rank before the solve. */
-    GM_OPT_POISON = 19      /* test hook, multi-process sharded solves: 1 = fill what a rank receives
+    GM_OPT_POISON = 19,     /* test hook, multi-process sharded solves: 1 = fill what a rank receives
                                with 0xFF before it arrives -- the split box engine's table (IPC / RCCL
                                transports) before every solve, the sparse engine's receive buffers
                                before every exchange -- so a halo or reply that never lands, or lands
@@ -161,6 +164,10 @@ enum {
                                rank 0 is held 50 ms -- solve 2 then differs from the oracle; 3 = the
                                same fault without the poisoning, which no digest can see (solve 2 reads
                                solve 1's identical bytes; tests/test_gpu_multiproc.py) */
+    GM_OPT_LOOPY = 20       /* GM_GAME_GRAPH contexts only (GM_E_ARG on any other): 0 (default) =
+                               gm_solve_graph refuses a cycle and a DRAW primitive; 1 = the loopy solve:
+                               frontier retrograde over the reverse graph, cycles allowed, what neither
+                               side can decide is DRAW (gm_solve_graph) */
 };
 
 /* Buffer roles for gm_adopt_buffer. */
@@ -176,7 +183,7 @@ typedef struct {
     int32_t n_tiers;        /* tiers walked */
     int32_t world;          /* ranks in the solve */
     double solve_ms;        /* wall time of the last gm_solve (host clock, device-synchronised) */
-    double forward_ms;      /* sparse path: forward expansion part */
+    double forward_ms;      /* sparse path: forward expansion part; loopy graph solve: building the reverse graph */
     double backward_ms;     /* retrograde part */
     double exchange_ms;     /* multi-GPU: time inside RCCL calls (host-observed) */
     uint64_t algo_bytes;    /* algorithmic HBM bytes of the solve (SURVEY §8d edge model) */
@@ -279,6 +286,17 @@ int gm_query_key(gm_ctx *ctx, const uint64_t *key_words, uint16_t *records, uint
  * A remoteness up to 0x3FFE always solves and one past 0x3FFF is GM_E_CAP.  After
  * any failed call the context holds no table (gm_export & co. return GM_E_STATE)
  * until the next solve succeeds.
+ * With GM_OPT_LOOPY 1 cycles and DRAW primitives are solved, not refused: the table is
+ * the least fixed point by levels.  Level 0 is the WIN and LOSS primitives; at level
+ * k >= 1 an undecided position with a LOSS child of remoteness k - 1 is WIN in k, one
+ * whose children are all WIN with largest remoteness k - 1 is LOSS in k, until a level
+ * decides nothing.  Then, over what is still undecided, level 0 is the TIE primitives
+ * and a position with a TIE child of remoteness k - 1 is TIE in k.  Everything left,
+ * and every DRAW primitive, is DRAW: record 0xC000.  On an acyclic graph without DRAW
+ * primitives the records equal the default mode's.  An undecided position without
+ * children, a code above 4 and the remoteness limits stay as above; gm_stats_t.n_tiers
+ * counts the levels of both phases that decided a position, and gm_draw_count the DRAW
+ * positions.
  * Replaces the reference's per-position job loop for arbitrary plugins
  * (src/new_process.py:37-265, GameState.expand src/game_state.py:33-41). */
 int gm_solve_graph(gm_ctx *ctx, uint64_t n, const uint8_t *primitive, const uint64_t *child_off,
@@ -288,6 +306,11 @@ int gm_solve_graph(gm_ctx *ctx, uint64_t n, const uint8_t *primitive, const uint
  * NULL only *n is set (the count).  Replaces reading the resolved/remote shelve
  * tables (src/cache_dict.py:38-79, src/new_process.py:76-78). */
 int gm_export(gm_ctx *ctx, uint64_t *keys, uint16_t *records, uint64_t cap, uint64_t *n);
+
+/* DRAW positions (record 0xC000) of the last solve: those a loopy graph solve
+ * (GM_OPT_LOOPY) left undecided plus its DRAW primitives; 0 after any other solve, of
+ * any engine.  GM_E_STATE before a solve or after a failed one. */
+int gm_draw_count(gm_ctx *ctx, uint64_t *n_draw);
 
 /* Records of n keys (0xFFFF for keys this rank does not hold: in a multi-process solve a rank
  * holds the keys it computed -- box engine: the boxes of gm_box_plan GM_BOXPLAN_BOXES, sparse
@@ -309,7 +332,8 @@ int gm_digest(gm_ctx *ctx, uint64_t *digest, uint64_t *n);
  * *n = positions counted: exactly the positions gm_digest counts for this context (the root's
  * region; every member of a stored representative's symmetry orbit; all virtual ranks; in a
  * multi-process solve the keys this rank holds, so the ranks' arrays add up to the one-GPU
- * answer).  One-word and multi-word key contexts alike.
+ * answer).  One-word and multi-word key contexts alike.  DRAW positions of a loopy graph solve
+ * have no row; they are counted in *n, so *n less the sum of counts is their number.
  * counts == NULL: only *n_rem and *n are set (the census is kept for the fill call that
  * follows, so a query and its fill read the table once).
  * cap < *n_rem: GM_E_CAP, with *n_rem and *n still set.
@@ -343,6 +367,13 @@ typedef struct {
  * the backward pass generates them, every one of them is visited, and a primitive child is
  * answered by primitive() without a lookup.  A pass does not rule out extra positions that the
  * root cannot reach.
+ * After a loopy graph solve (GM_OPT_LOOPY) the rule is the loopy one: a primitive carries
+ * (value, 0), DRAW included; an interior node's record is the reduction of its children's
+ * records under the preference LOSS (shortest) > TIE (shortest) > DRAW > WIN (longest), a
+ * best child DRAW making the parent DRAW.  A finite label is then sound by induction on its
+ * remoteness and every decided node forced to its label, so what remains is DRAW.
+ * missing_child is a child without a record, bad_value a record that differs from that
+ * reduction.
  * *n_bad = the sum of the five classes.  Up to cap offending keys are written to bad_key_words,
  * gm_key_words() words each, ascending: all of them when *n_bad <= cap, else any cap of them.
  * bad_key_words == NULL or cap == 0: counts only.  Nothing else leaves the device.

@@ -2,6 +2,7 @@
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
     python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
+                          [--loopy]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -13,6 +14,9 @@ intends for the root's canonical value, computed on the GPU by libgmsolve.so;
 positions by value and remoteness (gamesmanmpi_amd/analysis.py), ``--verify`` the check of the
 solved table against the game rules (gm_verify, gamesmanmpi_amd/verify.py: one line, then any
 offending positions; the exit status is non-zero when the table is inconsistent).
+``--loopy`` solves a game in which positions can repeat (explicit graph, GM_OPT_LOOPY): "Draw"
+is then a real answer, ``--remoteness`` prints ``DRAW`` alone for it and ``--analysis`` adds a
+line ``Draw  N`` under its table.
 """
 import argparse
 import os
@@ -37,12 +41,13 @@ def main(argv=None):
     p.add_argument("--remoteness", action="store_true")
     p.add_argument("--analysis", action="store_true")
     p.add_argument("--verify", action="store_true")
+    p.add_argument("--loopy", action="store_true")
     p.add_argument("--device", type=int, default=-1)
     args = p.parse_args(argv)
     args.engine = "auto"
     game, root = solver_launcher.prepare_game(args)
     from gamesmanmpi_amd import Solver
-    s = Solver(game, root, device=args.device)
+    s = Solver(game, root, device=args.device, loopy=True) if args.loopy else Solver(game, root, device=args.device)
     s.solve()
     print(MESSAGES[s.value])
     if args.remoteness:
@@ -50,6 +55,8 @@ def main(argv=None):
     if args.analysis:
         from gamesmanmpi_amd import analysis
         print(analysis.format_table(s.analysis()))
+        if args.loopy:
+            print("Draw  %d" % s.draw_count())
     status = 0
     if args.verify:
         from gamesmanmpi_amd import verify

@@ -38,7 +38,12 @@ Differences, on purpose:
   the exit status is non-zero when anything is inconsistent, and with ``-sd DIR`` rank 0
   writes ``DIR/stats/verify.json``.  Ranks that share one solve on rank 0 verify as one
   process does; a solve sharded over processes is refused before it starts, since no rank
-  holds the tables of its children's owners.
+  holds the tables of its children's owners;
+* ``--loopy`` is for games in which a position can repeat: the plugin is enumerated on the
+  host and solved as an explicit graph with cycles allowed (GM_OPT_LOOPY, one process); a
+  position neither side can decide is a draw, the root line of a drawn root is ``DRAW``
+  alone, ``--analysis`` adds a line ``Draw  N`` under its table and ``analysis.json`` a key
+  ``"draw"``.
 """
 import argparse
 import cProfile
@@ -76,6 +81,8 @@ def build_parser():
                    help="after the root line, print the positions by value and remoteness")
     p.add_argument("--verify", action="store_true",
                    help="after the root line, check the solved table against the game rules on the device")
+    p.add_argument("--loopy", action="store_true",
+                   help="solve a game with cycles: explicit graph, undecidable positions are DRAW")
     p.add_argument("--sd-format", choices=("auto", "npz", "reference", "both"), default="auto",
                    help="-sd output: npz table, the reference's shelve layout, or both (auto: both up to "
                         "%d positions, else npz)" % SHELVE_AUTO_LIMIT)
@@ -199,7 +206,11 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
         from gamesmanmpi_amd import dist
     engine = {"auto": None, "dense": _lib.ENGINE_DENSE, "sparse": _lib.ENGINE_SPARSE}[args.engine]
     device = args.device if args.device is not None else (local if plan == "sharded" else -1)
-    solver = Solver(game, root, device=device, engine=engine)
+    loopy = getattr(args, "loopy", False)
+    if loopy and plan == "sharded":
+        raise SystemExit("--loopy solves in one process: the graph engine is not sharded")
+    solver = Solver(game, root, device=device, engine=engine, loopy=True) if loopy else \
+        Solver(game, root, device=device, engine=engine)
     if plan == "sharded":
         dist.join(solver.ctx, rank, world)
     elif plan == "single" and solver.codec.game_id != _lib.GAME_GRAPH and world <= MAX_VIRTUAL_RANKS:
@@ -249,12 +260,16 @@ def report_analysis(args, solver, rank, world, plan, out):
     if rank != 0:
         return
     out.write(analysis.format_table(hist) + "\n")
+    loopy = getattr(args, "loopy", False)
+    if loopy:
+        out.write("Draw  %d\n" % solver.draw_count())
     out.flush()
     if args.statsdir:
         path = os.path.join(args.statsdir, "stats", "analysis.json")
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as f:
-            json.dump(analysis.as_json(hist), f, indent=1)
+            json.dump(dict(analysis.as_json(hist), draw=solver.draw_count()) if loopy else analysis.as_json(hist),
+                      f, indent=1)
             f.write("\n")
 
 
