@@ -51,7 +51,7 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
-           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count")
+           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import")
 
 
 class GMError(RuntimeError):
@@ -142,6 +142,7 @@ def lib():
         "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
         "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
         "gm_draw_count": (ctypes.c_int, [vp, P(u64)]),
+        "gm_import": (ctypes.c_int, [vp, vp, vp, vp, u64, P(u64), P(ctypes.c_uint16)]),
         "gm_stats": (ctypes.c_int, [vp, P(Stats)]),
         "gm_tier_counts": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int)]),
         "gm_adopt_buffer": (ctypes.c_int, [vp, ctypes.c_int, vp, u64]),

@@ -904,7 +904,9 @@ __global__ void sub_digest_kernel(const uint8_t *__restrict__ table, uint64_t sl
         bool in = true;
         for (int j = 0; j < heaps; j++) in &= ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
         if (!in) continue;
-        sum += digest_term(k, record_of_code(table[k]));
+        const uint8_t code = table[k];
+        if (!code) continue;   // a position an imported table does not hold (a solve fills the region)
+        sum += digest_term(k, record_of_code(code));
         cnt++;
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -1071,7 +1073,20 @@ static int launch_tiers(Ctx *c, DenseSub *d, bool timed) {
 
 static void dense_sub_free(Ctx *c);
 
-static int dense_sub_solve(Ctx *c, uint64_t root) {
+// positions per global tier (heap sum) of the full table
+static std::vector<uint64_t> sub_tier_counts(int heaps) {
+    std::vector<uint64_t> acc(1, 1);
+    for (int j = 0; j < heaps; j++) {
+        std::vector<uint64_t> nx(acc.size() + 15, 0);
+        for (size_t s = 0; s < acc.size(); s++)
+            for (int h = 0; h < 16; h++) nx[s + h] += acc[s];
+        acc.swap(nx);
+    }
+    return acc;
+}
+
+// the DenseSub a solve or an import from `root` with the context's options needs: the one held, or a new one
+static int dense_sub_ensure(Ctx *c, uint64_t root) {
     DenseSub *d = c->dsub;
     if (!d || d->heaps != c->sub.heaps || d->want_threads != c->sub_threads || d->want_x4 != c->sub_interleave ||
         d->want_order != c->sub_order || d->low != std::min(std::max(c->sub_low, 1), std::min(3, c->sub.heaps)) ||
@@ -1080,6 +1095,12 @@ static int dense_sub_solve(Ctx *c, uint64_t root) {
         d = c->dsub = new DenseSub();
         GM_TRY(prepare(c, d, root));
     }
+    return GM_OK;
+}
+
+static int dense_sub_solve(Ctx *c, uint64_t root) {
+    GM_TRY(dense_sub_ensure(c, root));
+    DenseSub *d = c->dsub;
 #ifdef GM_WK_TRACE
     static uint64_t *tbuf = nullptr;
     static uint32_t *tcnt = nullptr;
@@ -1140,17 +1161,7 @@ static int dense_sub_solve(Ctx *c, uint64_t root) {
     for (int j = 0; j < d->heaps; j++) n *= ((root >> (4 * j)) & 15u) + 1;
     c->n_positions = n;
     int ntiers = (int)d->tier_off.size() - 1;
-    // positions per global tier (heap sum) of the full table
-    {
-        std::vector<uint64_t> acc(1, 1);
-        for (int j = 0; j < d->heaps; j++) {
-            std::vector<uint64_t> nx(acc.size() + 15, 0);
-            for (size_t s = 0; s < acc.size(); s++)
-                for (int h = 0; h < 16; h++) nx[s + h] += acc[s];
-            acc.swap(nx);
-        }
-        c->tier_counts = acc;
-    }
+    c->tier_counts = sub_tier_counts(d->heaps);
     c->stats.n_positions = n;
     c->stats.n_primitive = 1;
     c->stats.n_tiers = ntiers;
@@ -1192,7 +1203,7 @@ static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
     for (uint64_t k = 0; k < d->slots; k++) {
         bool in = true;
         for (int i = 0; i < d->heaps && in; i++) in = ((k >> (4 * i)) & 15u) <= ((c->root >> (4 * i)) & 15u);
-        if (!in) continue;
+        if (!in || !h[k] || j >= cap) continue;   // code 0: a position an imported table does not hold
         keys[j] = k;
         recs[j] = record_of_code(h[k]);
         j++;
@@ -1282,8 +1293,88 @@ static void dense_sub_free(Ctx *c) {
     c->dsub = nullptr;
 }
 
+// gm_import: the 1-byte code of each record scattered to slot = key of a zeroed table (WIN R ->
+// R + 1, LOSS R -> 255 - R, gm_common.hpp).  The byte is set with an atomicOr on its aligned
+// 32-bit word -- it was 0, so the OR stores it, and a byte found non-zero is a key given twice.
+// The first offender goes out as index << 3 | reason through one atomicMin word.
+enum : uint32_t { SUBIMP_INVALID = 1, SUBIMP_REGION = 2, SUBIMP_RECORD = 3, SUBIMP_TWICE = 4 };
+__global__ __launch_bounds__(256) void sub_import_kernel(uint8_t *table, uint64_t slots, uint64_t root, int heaps,
+                                                         const uint64_t *__restrict__ keys,
+                                                         const uint16_t *__restrict__ recs, uint64_t n, uint64_t base,
+                                                         unsigned long long *first) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+        const uint64_t k = keys[i];
+        const uint16_t rec = recs[i];
+        uint32_t why = 0;
+        if (k >= slots) {
+            why = SUBIMP_INVALID;
+        } else {
+            bool in = true;
+            for (int j = 0; j < heaps; j++) in &= ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
+            const uint32_t val = rec >> 14, rem = rec & 0x3FFFu;
+            if (!in) why = SUBIMP_REGION;
+            else if (rec == REC_UNSOLVED || rem > 126u || val > (uint32_t)LOSS) why = SUBIMP_RECORD;   // gm_poke's rule
+            else {
+                const uint32_t code = val == (uint32_t)WIN ? rem + 1u : 255u - rem, sh = 8u * (uint32_t)(k & 3u);
+                const uint32_t old = atomicOr((uint32_t *)(table + (k & ~3ull)), code << sh);
+                if ((old >> sh) & 255u) why = SUBIMP_TWICE;
+            }
+        }
+        if (why) atomicMin(first, (unsigned long long)((base + i) << 3 | why));
+    }
+}
+
+static int dense_sub_import(Ctx *c, const void *keys_, const uint16_t *recs, uint64_t n) {
+    const uint64_t *keys = (const uint64_t *)keys_;
+    const uint64_t root = c->root;
+    GM_TRY(dense_sub_ensure(c, root));
+    DenseSub *d = c->dsub;
+    GM_HIP(hipMemsetAsync(d->table, 0, d->slots, c->stream));
+    DevBuf<unsigned long long> first;
+    GM_TRY(first.alloc(1));
+    GM_HIP(hipMemsetAsync(first, 0xFF, 8, c->stream));
+    const uint64_t chunk = std::min<uint64_t>(n, 1ull << 24);
+    DevBuf<uint64_t> dk;
+    DevBuf<uint16_t> dr;
+    GM_TRY(dk.alloc(chunk));
+    GM_TRY(dr.alloc(chunk));
+    for (uint64_t o = 0; o < n; o += chunk) {
+        const uint64_t m = std::min(chunk, n - o);
+        GM_HIP(hipMemcpyAsync(dk, keys + o, m * 8, hipMemcpyHostToDevice, c->stream));
+        GM_HIP(hipMemcpyAsync(dr, recs + o, m * 2, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(sub_import_kernel, dim3((unsigned)std::min<uint64_t>((m + 255) / 256, 8192)), dim3(256), 0,
+                           c->stream, d->table, d->slots, root, d->heaps, dk.p, dr.p, m, o, first.p);
+    }
+    GM_HIP(hipGetLastError());
+    unsigned long long f = 0;
+    GM_HIP(hipMemcpyAsync(&f, first, 8, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    if (f != ~0ull) {
+        const unsigned long long i = f >> 3, k = keys[i];
+        switch ((uint32_t)(f & 7)) {
+        case SUBIMP_INVALID: set_error("gm_import: key 0x%llx (index %llu) is not a valid position", k, i); return GM_E_KEY;
+        case SUBIMP_REGION:
+            set_error("gm_import: key 0x%llx (index %llu) is outside the root's region (a heap above the root's)", k, i);
+            return GM_E_KEY;
+        case SUBIMP_RECORD:
+            set_error("gm_import: key 0x%llx (index %llu) has record 0x%04x; the 1-byte codes hold WIN / LOSS with "
+                      "remoteness <= 126", k, i, recs[i]);
+            return GM_E_ARG;
+        }
+        set_error("gm_import: key 0x%llx (index %llu) is given twice", k, i);
+        return GM_E_ARG;
+    }
+    c->n_positions = n;
+    c->tier_counts = sub_tier_counts(d->heaps);
+    c->stats.n_positions = n;
+    c->stats.n_stored = n;
+    c->stats.n_tiers = (int)d->tier_off.size() - 1;
+    c->stats.table_bytes = d->slots;
+    return GM_OK;
+}
+
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
                  dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_table, dense_sub_free,
-                 dense_sub_verify, dense_sub_poke)
+                 dense_sub_verify, dense_sub_poke, dense_sub_import)
 
 }  // namespace gm

@@ -1385,8 +1385,28 @@ static void dist_sparse_free(Ctx *c) {
     c->dist_sp = nullptr;
 }
 
+// gm_import on a wide context (Othello 8x8, K128 keys): the state of a G = 1 solve -- one
+// loopback rank, its tier tables and t_root -- which is all the readers above look at
+// (sparse_tables.hpp tiers_import).  One-word contexts import into the one-GPU engines.
+static int dist_sparse_import(Ctx *c, const void *keys, const uint16_t *recs, uint64_t n) {
+    if (!c->wide) { set_error("gm_import: the hash-sharded engine imports 128-bit-key tables only"); return GM_E_ARG; }
+    dist_sparse_free(c);
+    DistSparseK<K128> *d = new DistSparseK<K128>();
+    c->dist_sp = d;
+    d->wide = true;
+    d->loopback = true;
+    d->G = 1;
+    d->S = DescOthello8::MAX_SKIP;
+    d->t_root = c->oth8.tier(c->root_wide);
+    d->ranks.resize(1);
+    GM_TRY(tiers_import(c, c->oth8, d->t_root, 0u, (const K128 *)keys, recs, n, d->ranks[0].tiers));
+    import_account(c, d->ranks[0].tiers);
+    d->gcount.assign(c->tier_counts.begin(), c->tier_counts.end());
+    return GM_OK;
+}
+
 GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
                  dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, nullptr, dist_sparse_free,
-                 dist_sparse_verify, dist_sparse_poke)
+                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import)
 
 }  // namespace gm

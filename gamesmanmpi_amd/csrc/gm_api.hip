@@ -628,6 +628,92 @@ static int need_solved(gm_ctx *h) {
     return GM_OK;
 }
 
+int gm_import(gm_ctx *h, const uint64_t *root_words, const uint64_t *key_words, const uint16_t *records, uint64_t n,
+              uint64_t *n_positions, uint16_t *root_record) {
+    if (!h) return GM_E_ARG;
+    Ctx *c = &h->c;
+    // from here on a refusal leaves the context without a table, as a failed solve does
+    c->solved = false;
+    c->solved_by = nullptr;
+    c->hist_is_kept = false;
+    c->n_draw = 0;
+    if (!root_words || !key_words || !records) { set_error("gm_import: root_words, key_words or records is NULL"); return GM_E_ARG; }
+    if (!n) { set_error("gm_import: n is 0"); return GM_E_ARG; }
+    if (c->game == GM_GAME_GRAPH) {
+        set_error("gm_import: the keys of a GM_GAME_GRAPH table are the host walk's numbering, which a table does not carry");
+        return GM_E_GAME;
+    }
+    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
+    if (c->world > 1 || c->virtual_ranks > 1) {
+        set_error("gm_import builds the whole table in one context: not for rank %d of %d processes or %d virtual ranks",
+                  c->rank, c->world, c->virtual_ranks);
+        return GM_E_ARG;
+    }
+    if (!c->wide && c->engine_opt == GM_ENGINE_DIST_SPARSE) {
+        set_error("gm_import: GM_ENGINE_DIST_SPARSE on a one-word context; the one-GPU engines import its tables");
+        return GM_E_ARG;
+    }
+    const Engine *e = c->wide ? &dist_sparse_engine : choose_engine(c, false);
+    if (e == &dense_box_engine) {
+        set_error("gm_import: the box engine's tables are not imported; set GM_OPT_SUB_INTERLEAVE 10 for the block engine");
+        return GM_E_GAME;
+    }
+    if (!e->import_) { set_error("gm_import: this engine's tables are not imported"); return GM_E_GAME; }
+    K128 root_wide{0, 0};
+    if (c->wide) {
+        if (!DescOthello8::from_words(root_words, &root_wide)) {
+            set_error("root key is not a valid position (an 8x8 Othello position keeps its four centre squares)");
+            return GM_E_KEY;
+        }
+    } else if (!key_valid(c, root_words[0])) {
+        set_error("root key 0x%llx is not a valid position", (unsigned long long)root_words[0]);
+        return GM_E_KEY;
+    }
+    GM_HIP(hipSetDevice(c->device));
+    c->stats = gm_stats_t{};
+    c->stats.world = 1;
+    c->root = c->wide ? 0 : root_words[0];
+    c->root_wide = root_wide;
+    // the symmetry reduction of a solve from this root (gm_solve)
+    if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(c->root) == c->root) ? 1u : 0u;
+    if (c->game == GM_GAME_OTHELLO && !c->wide) c->oth.sym = c->symmetry ? c->oth.stabilizer(c->root) : 0u;
+    if (e == &dense_sub_engine)
+        for (const Engine *o : {&dense_box_engine, &dist_box_engine}) o->free_(c);
+    std::vector<K128> wide_keys;
+    if (c->wide) {
+        wide_keys.resize(n);
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t *w = key_words + (size_t)WIDE_WORDS * i;
+            if (!DescOthello8::from_words(w, &wide_keys[i])) {
+                set_error("gm_import: key 0x%llx 0x%llx 0x%llx (index %llu) is not a valid position", (unsigned long long)w[0],
+                          (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)i);
+                return GM_E_KEY;
+            }
+        }
+    }
+    const double t0 = now_ms();
+    const int rc = e->import_(c, c->wide ? (const void *)wide_keys.data() : (const void *)key_words, records, n);
+    if (rc != GM_OK) {
+        e->free_(c);
+        return rc;
+    }
+    c->stats.solve_ms = now_ms() - t0;
+    c->stats.engine = e->id;
+    // the stored record of the root, 0xFFFF when the table does not hold it (gm_verify: root_ok = 0)
+    uint16_t rr = REC_UNSOLVED;
+    const int rq = c->wide ? dist_sparse_query_wide(c, &c->root_wide, &rr, 1) : e->query(c, &c->root, &rr, 1);
+    if (rq != GM_OK) {
+        e->free_(c);
+        return rq;
+    }
+    c->root_record = rr;
+    c->solved = true;
+    c->solved_by = e;
+    if (n_positions) *n_positions = c->n_positions;
+    if (root_record) *root_record = c->root_record;
+    return GM_OK;
+}
+
 int gm_export(gm_ctx *h, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     GM_TRY(need_solved(h));
     if (!n || (keys && !recs)) return GM_E_ARG;

@@ -159,6 +159,10 @@ struct Engine {
     void (*free_)(Ctx *c);
     int (*verify)(Ctx *c, const VerifyDev &v);         // gm_verify: every stored position into the accumulator
     int (*poke)(Ctx *c, const uint64_t *words, uint16_t rec);   // gm_poke: one stored record overwritten (test hook)
+    // gm_import: the table of root c->root (c->root_wide) built from n (key, record) pairs; keys are
+    // uint64_t, or K128 on a wide context.  Sets n_positions, tier_counts and the table's share of
+    // stats; on failure the caller frees the engine.  null: the engine's tables cannot be imported
+    int (*import_)(Ctx *c, const void *keys, const uint16_t *recs, uint64_t n);
 };
 // A record is host data, defined in the host pass only: the device pass of a translation unit
 // would emit a const record too, with references to the host functions it names.

@@ -205,8 +205,52 @@ static void small_dense_free(Ctx *c) {
     c->sd = nullptr;
 }
 
+// gm_import: the record table filled on the host (19,683 slots, absent ones 0xFFFF) and copied
+// to the device, where gm_verify reads it
+static int small_dense_import(Ctx *c, const void *keys_, const uint16_t *recs, uint64_t n) {
+    if (c->game != GM_GAME_TTT) { set_error("small dense engine supports tic-tac-toe only"); return GM_E_GAME; }
+    const uint64_t *keys = (const uint64_t *)keys_;
+    SmallDense *s = c->sd;
+    if (!s) {
+        s = c->sd = new SmallDense();
+        s->slots = DescTTT::SLOTS;
+        GM_HIP(hipMalloc(&s->d_rec, s->slots * 2));
+        GM_HIP(hipMalloc(&s->d_info, 16));
+    }
+    const int64_t t_root = c->ttt.tier(c->root);
+    s->h_rec.assign(s->slots, REC_UNSOLVED);
+    c->tier_counts.assign(10, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t k = keys[i];
+        const unsigned long long kk = k, ii = i;
+        if (!c->ttt.valid(k)) {
+            set_error("gm_import: key 0x%llx (index %llu) is not a valid position", kk, ii);
+            return GM_E_KEY;
+        }
+        if (c->ttt.tier(k) < t_root) {
+            set_error("gm_import: key 0x%llx (index %llu) lies in a tier above the root's", kk, ii);
+            return GM_E_KEY;
+        }
+        if (recs[i] == REC_UNSOLVED || (recs[i] >> 14) > TIE) {
+            set_error("gm_import: key 0x%llx (index %llu) has record 0x%04x, not a WIN / LOSS / TIE record", kk, ii, recs[i]);
+            return GM_E_ARG;
+        }
+        if (s->h_rec[k] != REC_UNSOLVED) { set_error("gm_import: key 0x%llx is given twice", kk); return GM_E_ARG; }
+        s->h_rec[k] = recs[i];
+        c->tier_counts[c->ttt.tier(k)]++;
+    }
+    GM_HIP(hipMemcpyAsync(s->d_rec, s->h_rec.data(), s->slots * 2, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    c->n_positions = n;
+    c->stats.n_positions = n;
+    c->stats.n_stored = n;
+    c->stats.n_tiers = 10;
+    c->stats.table_bytes = s->slots * 2;
+    return GM_OK;
+}
+
 GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
                  small_dense_query, small_dense_digest, small_dense_histogram, nullptr, small_dense_free,
-                 small_dense_verify, small_dense_poke)
+                 small_dense_verify, small_dense_poke, small_dense_import)
 
 }  // namespace gm

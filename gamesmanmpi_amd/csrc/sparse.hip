@@ -871,7 +871,22 @@ static void sparse_free(Ctx *c) {
     c->sp = nullptr;
 }
 
+// gm_import: tier tables from (key, record) pairs (sparse_tables.hpp tiers_import), with the
+// home function a solve would use.  No interior lists and no plan: the next gm_solve on the
+// context runs a synced solve and never replays over imported tables.
+static int sparse_import(Ctx *c, const void *keys, const uint16_t *recs, uint64_t n) {
+    return with_desc(c, [&](const auto &d) {
+        sparse_free(c);
+        Sparse *sp = c->sp = new Sparse();
+        sp->t_root = d.tier(c->root);
+        GM_TRY(tiers_import(c, d, sp->t_root, home_loc(c), (const uint64_t *)keys, recs, n, sp->tiers));
+        import_account(c, sp->tiers);
+        return (int)GM_OK;
+    });
+}
+
 GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
-                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free, sparse_verify, sparse_poke)
+                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free, sparse_verify, sparse_poke,
+                 sparse_import)
 
 }  // namespace gm

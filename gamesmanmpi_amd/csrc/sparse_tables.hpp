@@ -838,4 +838,367 @@ inline int tiers_poke(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>>
     return GM_OK;
 }
 
+// ------------------------------------------------------------------ import
+// gm_import: the tier tables a solve from the root would hold had it produced exactly the given
+// (key, record) pairs -- what the readers above look at, built without a solve.  Four passes
+// over the input, which stays on the device in chunks of at most IMPORT_CHUNK keys (a table of
+// more is uploaded again by each pass):
+//   scan     one lane per key: valid(), tier - t_root in [0, IMPORT_MAX_TIERS), the record a
+//            WIN / LOSS / TIE one; keys counted per tier -- an exact upper bound of the tier's
+//            table, so nothing is predicted
+//   insert   canon(key) into its tier's table (front_insert), fresh inserts counted per tier
+//   score    after the insert kernel: the slot's score word goes 0 -> score_of_record by
+//            atomicCAS; an old value that is neither 0 nor the same score is a conflict (two
+//            members of one orbit, or one key twice, with different records)
+//   census   per table: stored keys and the positions their orbits stand for (count, count_all)
+// A key that breaks a rule is reported as index << 3 | reason through one atomicMin word, so the
+// host names the first offender.  The per-tier counters are LDS bins, flushed with one global
+// atomic per non-empty bin per workgroup.  No kernel waits on another: every loop ends at the
+// list's length or a probe limit.
+constexpr int IMPORT_MAX_TIERS = 1024;
+constexpr uint64_t IMPORT_CHUNK = 1ull << 24;
+enum : uint32_t { IMP_INVALID = 1, IMP_TIER = 2, IMP_DEPTH = 3, IMP_RECORD = 4, IMP_CONFLICT = 5, IMP_LOST = 6 };
+
+namespace {
+
+__device__ __forceinline__ void import_note(unsigned long long *first, uint64_t index, uint32_t why) {
+    atomicMin(first, (unsigned long long)(index << 3 | why));
+}
+
+__device__ __forceinline__ void tier_bins_clear(uint32_t *bins) {
+    for (int i = threadIdx.x; i < IMPORT_MAX_TIERS; i += blockDim.x) bins[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void tier_bins_flush(const uint32_t *bins, unsigned long long *out) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < IMPORT_MAX_TIERS; i += blockDim.x)
+        if (bins[i]) atomicAdd(out + i, (unsigned long long)bins[i]);
+}
+
+template <class D>
+__global__ __launch_bounds__(256) void import_scan_kernel(D d, int64_t t_root, const key_t<D> *__restrict__ keys,
+                                                          const uint16_t *__restrict__ recs, uint64_t n, uint64_t base,
+                                                          unsigned long long *per_tier, unsigned long long *first) {
+    __shared__ uint32_t bins[IMPORT_MAX_TIERS];
+    tier_bins_clear(bins);
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+        const key_t<D> k = keys[i];
+        const uint16_t rec = recs[i];
+        uint32_t why = 0;
+        int64_t t = 0;
+        if (!d.valid(k)) {
+            why = IMP_INVALID;
+        } else {
+            t = d.tier(k) - t_root;
+            if (t < 0) why = IMP_TIER;
+            else if (t >= IMPORT_MAX_TIERS) why = IMP_DEPTH;
+            else if (rec == REC_UNSOLVED || (rec >> 14) > TIE) why = IMP_RECORD;
+        }
+        if (why) import_note(first, base + i, why);
+        else atomicAdd(&bins[t], 1u);
+    }
+    tier_bins_flush(bins, per_tier);
+}
+
+template <class D>
+__global__ __launch_bounds__(256) void import_insert_kernel(D d, int64_t t_root, const key_t<D> *__restrict__ keys,
+                                                            uint64_t n,
+                                                            const typename KT<key_t<D>>::Front *__restrict__ fronts,
+                                                            unsigned long long *fresh, uint32_t *err) {
+    __shared__ uint32_t bins[IMPORT_MAX_TIERS];
+    tier_bins_clear(bins);
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+        if (*(volatile uint32_t *)err & DEV_ERR_TABLE_FULL) break;   // the pass is re-run into larger tables
+        const key_t<D> k = d.canon(keys[i]);
+        const int64_t t = d.tier(k) - t_root;   // in range: the scan passed
+        if (front_insert(fronts[t], k, err)) atomicAdd(&bins[t], 1u);
+    }
+    tier_bins_flush(bins, fresh);
+}
+
+template <class D>
+__global__ __launch_bounds__(256) void import_score_kernel(D d, int64_t t_root, const key_t<D> *__restrict__ keys,
+                                                           const uint16_t *__restrict__ recs, uint64_t n, uint64_t base,
+                                                           const typename KT<key_t<D>>::Res *__restrict__ tabs,
+                                                           unsigned long long *first) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
+        const key_t<D> k = d.canon(keys[i]);
+        const typename KT<key_t<D>>::Res r = tabs[d.tier(k) - t_root];
+        const int64_t at = res_find_slot(r, k);
+        if (at < 0) { import_note(first, base + i, IMP_LOST); continue; }
+        const unsigned long long sc = score_of_record(recs[i]);
+        const unsigned long long old = atomicCAS((unsigned long long *)&r.s[at].score, 0ull, sc);
+        if (old != 0ull && old != sc) import_note(first, base + i, IMP_CONFLICT);
+    }
+}
+
+// out[0] += stored keys, out[1] += the positions their orbits stand for
+template <class D>
+__global__ __launch_bounds__(256) void import_census_kernel(D d, const typename KT<key_t<D>>::Slot *__restrict__ s,
+                                                            uint64_t cap, unsigned long long *out) {
+    using K = key_t<D>;
+    uint64_t cnt = 0, all = 0;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256ull) {
+        const K key = slot_key(s[i]);
+        if (key_empty(key)) continue;
+        cnt++;
+        d.orbit(key, [&](const K &) { all++; });
+    }
+    block_add(out, cnt);
+    block_add(out + 1, all);
+}
+
+}  // namespace
+
+// a key as gm_last_error shows it: its ABI words in hex, least significant first
+inline std::string key_hex(uint64_t k) {
+    char b[32];
+    snprintf(b, sizeof b, "0x%llx", (unsigned long long)k);
+    return b;
+}
+inline std::string key_hex(const K128 &k) {
+    uint64_t w[3];
+    DescOthello8::to_words(k, w);
+    char b[96];
+    snprintf(b, sizeof b, "0x%llx 0x%llx 0x%llx", (unsigned long long)w[0], (unsigned long long)w[1],
+             (unsigned long long)w[2]);
+    return b;
+}
+
+// the refusal of the key an import kernel noted (index << 3 | reason)
+template <class K>
+inline int import_refuse(unsigned long long first, const K *keys, const uint16_t *recs) {
+    const uint64_t i = first >> 3;
+    const std::string k = key_hex(keys[i]);
+    switch ((uint32_t)(first & 7)) {
+    case IMP_INVALID:
+        set_error("gm_import: key %s (index %llu) is not a valid position", k.c_str(), (unsigned long long)i);
+        return GM_E_KEY;
+    case IMP_TIER:
+        set_error("gm_import: key %s (index %llu) lies in a tier above the root's", k.c_str(), (unsigned long long)i);
+        return GM_E_KEY;
+    case IMP_DEPTH:
+        set_error("gm_import: key %s (index %llu) lies %d or more tiers below the root", k.c_str(), (unsigned long long)i,
+                  IMPORT_MAX_TIERS);
+        return GM_E_CAP;
+    case IMP_RECORD:
+        set_error("gm_import: key %s (index %llu) has record 0x%04x, not a WIN / LOSS / TIE record", k.c_str(),
+                  (unsigned long long)i, recs[i]);
+        return GM_E_ARG;
+    case IMP_CONFLICT:
+        set_error("gm_import: key %s (index %llu) is given twice, or shares a symmetry orbit with another key, with "
+                  "different records", k.c_str(), (unsigned long long)i);
+        return GM_E_ARG;
+    }
+    set_error("gm_import: key %s (index %llu) was not found after its insert", k.c_str(), (unsigned long long)i);
+    return GM_E_STATE;
+}
+
+// GM_TRACE: the phases of an import by events (upload, scan, insert, score, census)
+struct ImportClock {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms[5] = {0, 0, 0, 0, 0};
+    bool on = false;
+    hipStream_t st = nullptr;
+    ImportClock(hipStream_t s, bool enable) : st(s) {
+        on = enable && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    }
+    ~ImportClock() {
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void begin() {
+        if (on) (void)hipEventRecord(ev[0], st);
+    }
+    void end(int phase) {
+        if (!on) return;
+        float t = 0;
+        (void)hipEventRecord(ev[1], st);
+        if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms[phase] += t;
+    }
+};
+
+// Build `tiers` (empty on entry) from n (key, record) pairs; on GM_OK every tier has its table,
+// count, count_all, fcount = count and no interior list.  The caller frees `tiers` on failure.
+template <class D>
+inline int tiers_import(Ctx *c, const D &d, int64_t t_root, uint32_t loc, const key_t<D> *keys, const uint16_t *recs,
+                        uint64_t n, std::vector<SpTierT<key_t<D>>> &tiers) {
+    using K = key_t<D>;
+    using Front = typename KT<K>::Front;
+    using Res = typename KT<K>::Res;
+    using Slot = typename KT<K>::Slot;
+    constexpr int NT = IMPORT_MAX_TIERS;
+    // GM_TEST_IMPORT_CHUNK: tests use a small chunk to drive the re-upload path with a small table
+    const char *tc = getenv("GM_TEST_IMPORT_CHUNK");
+    const uint64_t limit = tc && atoll(tc) > 0 ? std::min<uint64_t>(atoll(tc), IMPORT_CHUNK) : IMPORT_CHUNK;
+    const uint64_t chunk = std::min(n, limit);
+    const bool resident = n <= chunk;   // one upload serves every pass
+    ImportClock clk(c->stream, trace_on());
+    DevBuf<K> dk;
+    DevBuf<uint16_t> dr;
+    DevBuf<unsigned long long> acc;   // [0] first offender, [1, NT] keys per tier, (NT, 2 NT] fresh inserts per tier
+    DevBuf<uint32_t> derr;
+    GM_TRY(dk.alloc(chunk));
+    GM_TRY(dr.alloc(chunk));
+    GM_TRY(acc.alloc(1 + 2 * NT));
+    GM_TRY(derr.alloc(1));
+    auto upload = [&](uint64_t o, uint64_t m, bool with_recs) -> int {
+        clk.begin();
+        GM_HIP(hipMemcpyAsync(dk, keys + o, m * sizeof(K), hipMemcpyHostToDevice, c->stream));
+        if (with_recs) GM_HIP(hipMemcpyAsync(dr, recs + o, m * 2, hipMemcpyHostToDevice, c->stream));
+        clk.end(0);
+        return GM_OK;
+    };
+    std::vector<unsigned long long> h(1 + 2 * NT);
+
+    // ---------------- scan
+    GM_HIP(hipMemsetAsync(acc, 0xFF, 8, c->stream));
+    GM_HIP(hipMemsetAsync(acc.p + 1, 0, 2 * NT * 8, c->stream));
+    for (uint64_t o = 0; o < n; o += chunk) {
+        const uint64_t m = std::min(chunk, n - o);
+        GM_TRY(upload(o, m, true));
+        clk.begin();
+        hipLaunchKernelGGL(import_scan_kernel<D>, dim3(grid_counted(m)), dim3(256), 0, c->stream, d, t_root, dk.p, dr.p, m,
+                           o, acc.p + 1, acc.p);
+        clk.end(1);
+    }
+    GM_HIP(hipGetLastError());
+    GM_HIP(hipMemcpyAsync(h.data(), acc, (1 + NT) * 8, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    if (h[0] != ~0ull) return import_refuse(h[0], keys, recs);
+    size_t ntiers = 0;
+    for (size_t t = 0; t < (size_t)NT; t++)
+        if (h[1 + t]) ntiers = t + 1;
+    tiers.assign(ntiers, SpTierT<K>{});
+    std::vector<uint64_t> offered(ntiers);
+    for (size_t t = 0; t < ntiers; t++) {
+        offered[t] = h[1 + t];
+        tiers[t].loc = loc;
+        tiers[t].tier = t_root + (int64_t)t;
+        if (!offered[t]) continue;
+        // GM_TEST_IMPORT_TIGHT: tests start from tables a quarter of the size, which fill up
+        // (MAX_PROBE) and drive the re-run below
+        tiers[t].cap = getenv("GM_TEST_IMPORT_TIGHT") ? std::max<uint64_t>(64, offered[t] / 4) : table_cap_for(offered[t]);
+        GM_TRY(tier_alloc(c, &tiers[t].slots, tiers[t].cap));
+    }
+
+    // ---------------- insert (a full table: one re-run into tables of twice the planned size)
+    DevBuf<Front> fronts;
+    DevBuf<Res> tabs;
+    GM_TRY(fronts.alloc(ntiers));
+    GM_TRY(tabs.alloc(ntiers));
+    for (int attempt = 0;; attempt++) {
+        std::vector<Front> hf(ntiers);
+        for (size_t t = 0; t < ntiers; t++)
+            hf[t] = Front{tiers[t].slots, tiers[t].cap, nullptr, eff_loc(tiers[t].loc, tiers[t].cap)};
+        GM_HIP(hipMemcpyAsync(fronts, hf.data(), ntiers * sizeof(Front), hipMemcpyHostToDevice, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));   // hf leaves scope
+        GM_HIP(hipMemsetAsync(acc.p + 1 + NT, 0, NT * 8, c->stream));
+        GM_HIP(hipMemsetAsync(derr, 0, 4, c->stream));
+        for (uint64_t o = 0; o < n; o += chunk) {
+            const uint64_t m = std::min(chunk, n - o);
+            if (!resident) GM_TRY(upload(o, m, false));
+            clk.begin();
+            hipLaunchKernelGGL(import_insert_kernel<D>, dim3(grid_for(m)), dim3(256), 0, c->stream, d, t_root, dk.p, m,
+                               fronts.p, acc.p + 1 + NT, derr.p);
+            clk.end(2);
+        }
+        GM_HIP(hipGetLastError());
+        uint32_t e = 0;
+        GM_HIP(hipMemcpyAsync(&e, derr, 4, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipMemcpyAsync(h.data() + 1 + NT, acc.p + 1 + NT, NT * 8, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));
+        if (!e) break;
+        if (e != DEV_ERR_TABLE_FULL || attempt) return dev_error_to_gm(e);
+        for (size_t t = 0; t < ntiers; t++) {
+            if (!tiers[t].cap) continue;
+            dev_free(c, tiers[t].slots);
+            tiers[t].slots = nullptr;
+            tiers[t].cap = 2 * table_cap_for(offered[t]);
+            GM_TRY(tier_alloc(c, &tiers[t].slots, tiers[t].cap));
+        }
+    }
+
+    // ---------------- score
+    {
+        std::vector<Res> hr(ntiers);
+        for (size_t t = 0; t < ntiers; t++) hr[t] = res_ref_of(tiers[t]);
+        GM_HIP(hipMemcpyAsync(tabs, hr.data(), ntiers * sizeof(Res), hipMemcpyHostToDevice, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));   // hr leaves scope
+    }
+    for (uint64_t o = 0; o < n; o += chunk) {
+        const uint64_t m = std::min(chunk, n - o);
+        if (!resident) GM_TRY(upload(o, m, true));
+        clk.begin();
+        hipLaunchKernelGGL(import_score_kernel<D>, dim3(grid_for(m)), dim3(256), 0, c->stream, d, t_root, dk.p, dr.p, m, o,
+                           tabs.p, acc.p);
+        clk.end(3);
+    }
+    GM_HIP(hipGetLastError());
+    GM_HIP(hipMemcpyAsync(h.data(), acc, 8, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    if (h[0] != ~0ull) return import_refuse(h[0], keys, recs);
+
+    // ---------------- census
+    DevBuf<unsigned long long> cen;
+    GM_TRY(cen.alloc(2 * ntiers));
+    GM_HIP(hipMemsetAsync(cen, 0, 2 * ntiers * 8, c->stream));
+    clk.begin();
+    for (size_t t = 0; t < ntiers; t++)
+        if (tiers[t].cap)
+            hipLaunchKernelGGL(import_census_kernel<D>, dim3(grid_counted(tiers[t].cap)), dim3(256), 0, c->stream, d,
+                               (const Slot *)tiers[t].slots, tiers[t].cap, cen.p + 2 * t);
+    clk.end(4);
+    GM_HIP(hipGetLastError());
+    std::vector<unsigned long long> hc(2 * ntiers);
+    GM_HIP(hipMemcpyAsync(hc.data(), cen, hc.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    uint64_t all = 0;
+    for (size_t t = 0; t < ntiers; t++) {
+        if (hc[2 * t] != h[1 + NT + t]) {
+            set_error("gm_import: tier %zu holds %llu keys after %llu fresh inserts", t, hc[2 * t], h[1 + NT + t]);
+            return GM_E_STATE;
+        }
+        tiers[t].count = tiers[t].fcount = hc[2 * t];
+        tiers[t].count_all = hc[2 * t + 1];
+        all += hc[2 * t + 1];
+    }
+    if (clk.on)
+        fprintf(stderr, "[gm] import of %llu keys: upload %.3f scan %.3f insert %.3f score %.3f census %.3f ms\n",
+                (unsigned long long)n, clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4]);
+    if (all != n) {
+        // the stored representatives' orbits do not add up to the input: name a key given twice, if any
+        std::vector<K> s(keys, keys + n);
+        std::sort(s.begin(), s.end(), [](const K &a, const K &b) { return a < b; });
+        for (uint64_t i = 1; i < n; i++)
+            if (s[i] == s[i - 1]) {
+                set_error("gm_import: key %s is given twice", key_hex(s[i]).c_str());
+                return GM_E_ARG;
+            }
+        set_error("gm_import: %llu keys, but the stored representatives' orbits hold %llu positions (first key %s): "
+                  "duplicate keys or incomplete orbits; GM_OPT_SYMMETRY 0 imports the keys as given",
+                  (unsigned long long)n, (unsigned long long)all, key_hex(keys[0]).c_str());
+        return GM_E_ARG;
+    }
+    return GM_OK;
+}
+
+// what gm_import reports of imported tier tables: positions, per-tier counts, table bytes
+template <class K>
+inline void import_account(Ctx *c, const std::vector<SpTierT<K>> &tiers) {
+    uint64_t n = 0, stored = 0, tb = 0;
+    c->tier_counts.clear();
+    for (auto &T : tiers) {
+        stored += T.count;
+        n += T.count_all;
+        tb += T.cap * sizeof(typename KT<K>::Slot);
+        c->tier_counts.push_back(T.count_all);
+    }
+    c->n_positions = n;
+    c->stats.n_positions = n;
+    c->stats.n_stored = stored;
+    c->stats.n_tiers = (int32_t)tiers.size();
+    c->stats.table_bytes = tb;
+}
+
 }  // namespace gm

@@ -13,6 +13,8 @@ where a position lives on rank ``md5(str(pos)) % world_size``
 keys past 64 bits) in that layout, so tooling that
 reads the reference's ``-sd`` directory reads ours; ``read_reference_tables``
 reads it back (tests, and resuming from a reference run's tables).
+``read_npz_tables`` reads the other ``-sd`` output, ``stats/<rank>/table.npz``, back as the
+(keys, records) that ``Solver.load`` / ``gm_import`` put onto the device.
 """
 import hashlib
 import os
@@ -68,6 +70,44 @@ def write_reference_tables(statsdir, codec, keys, records, world_size=1):
             a.close()
             b.close()
     return counts
+
+
+def read_npz_tables(statsdir):
+    """(keys, records, meta) of every ``<statsdir>/stats/<rank>/table.npz`` (what ``-sd``
+    writes through solver.dump_table), concatenated in rank order: the input of
+    ``Solver.load`` / ``gm_import``.  ``meta`` is the files' common metadata dict (game, codec,
+    params); the parts must agree on ``codec`` and ``params`` (ValueError otherwise)."""
+    import ast
+    base = os.path.join(statsdir or "", "stats")
+    ranks = sorted(int(d) for d in (os.listdir(base) if os.path.isdir(base) else ())
+                   if d.isdigit() and os.path.exists(os.path.join(base, d, "table.npz")))
+    if not ranks:
+        raise FileNotFoundError("no stats/<rank>/table.npz under %r" % statsdir)
+    keys, recs, meta = [], [], None
+    for r in ranks:
+        path = os.path.join(base, str(r), "table.npz")
+        with np.load(path) as z:
+            k = np.asarray(z["keys"], dtype=np.uint64)
+            v = np.asarray(z["records"], dtype=np.uint16)
+            m = ast.literal_eval(str(z["meta"])) if "meta" in z.files else {}
+        if not isinstance(m, dict):
+            raise ValueError("%s: meta is not a dict" % path)
+        if len(k) != len(v):
+            raise ValueError("%s: %d keys, %d records" % (path, len(k), len(v)))
+        m = dict(m, params=tuple(m.get("params", ())))
+        if meta is None:
+            meta = m
+        elif (m.get("codec"), m["params"]) != (meta.get("codec"), meta["params"]):
+            raise ValueError("%s is a table of codec %r %r, rank %d's of %r %r"
+                             % (path, m.get("codec"), m["params"], ranks[0], meta.get("codec"), meta["params"]))
+        if len(k):
+            keys.append(k)
+            recs.append(v)
+    if not keys:
+        return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint16), meta
+    if len({k.ndim for k in keys}) != 1:
+        raise ValueError("%s: the parts' keys differ in width" % base)
+    return np.concatenate(keys), np.concatenate(recs), meta
 
 
 def read_reference_tables(statsdir, world_size=1):

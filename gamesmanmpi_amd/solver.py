@@ -107,6 +107,22 @@ class Context:
             _lib.check(self.L.gm_solve(self.h, root, ctypes.byref(n), ctypes.byref(r)))
         return n.value, r.value
 
+    def import_table(self, keys, records, root):
+        """gm_import: load (keys, records) as the table of a solve from `root`.  Keys as query()
+        takes them, in any order.  Returns (n_positions, root record; 0xFFFF when the root is
+        not among the keys)."""
+        keys = self.key_array(keys)
+        recs = np.ascontiguousarray(records, dtype=np.uint16)
+        if len(recs) != len(keys):
+            raise ValueError("import_table: %d keys, %d records" % (len(keys), len(recs)))
+        w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(root, self.words))
+        n = ctypes.c_uint64()
+        r = ctypes.c_uint16()
+        _lib.check(self.L.gm_import(self.h, w, keys.ctypes.data if len(keys) else None,
+                                    recs.ctypes.data if len(recs) else None, len(keys), ctypes.byref(n),
+                                    ctypes.byref(r)))
+        return n.value, r.value
+
     def key_array(self, keys):
         """Keys (Python ints, or an (n, words) uint64 array) -> the array gm_query_key takes."""
         if self.words == 1:
@@ -314,6 +330,29 @@ class Solver:
         else:
             self.n_positions, self.root_record = self.ctx.solve(self.root_key)
         return self.n_positions, self.root_record
+
+    def load(self, keys, records):
+        """In place of solve(): load a stored table of this game and root onto the device
+        (gm_import).  lookup(), table(), analysis(), verify() and moves() then answer for it.
+        The root record is 0xFFFF when the table does not hold the root."""
+        if self.codec.game_id == _lib.GAME_GRAPH:
+            raise NoDescriptor("a stored table loads into a descriptor game only: the keys of a graph solve are "
+                               "the host walk's numbering, which a table does not carry")
+        self.n_positions, self.root_record = self.ctx.import_table(keys, records, self.root_key)
+        return self.n_positions, self.root_record
+
+    def load_statsdir(self, statsdir):
+        """load() of every ``stats/<rank>/table.npz`` under `statsdir` (what ``-sd`` writes; a
+        sharded solve's ranks each wrote their share).  The files must be of this solver's codec."""
+        if self.codec.game_id == _lib.GAME_GRAPH:
+            raise NoDescriptor("a stored table loads into a descriptor game only")
+        from .persist import read_npz_tables
+        keys, recs, meta = read_npz_tables(statsdir)
+        mine = (self.codec.name, tuple(self.codec.params))
+        if (meta.get("codec"), tuple(meta.get("params", ()))) != mine:
+            raise ValueError("%s holds a table of codec %r with params %r; this solver's codec is %r with %r"
+                             % (statsdir, meta.get("codec"), meta.get("params"), mine[0], mine[1]))
+        return self.load(keys, recs)
 
     @property
     def value(self):

@@ -392,6 +392,39 @@ int gm_verify(gm_ctx *ctx, gm_verify_t *out, uint64_t *bad_key_words, uint64_t c
  * solve rewrites every table. */
 int gm_poke(gm_ctx *ctx, const uint64_t *key_words, uint16_t record);
 
+/* Load a saved table onto the device: n (key, record) pairs -- key_words holds n x
+ * gm_key_words() words, in any order; records are u16 records -- become the table a solve from
+ * root_words would hold had it produced exactly these records.  The context is left as a
+ * successful gm_solve / gm_solve_key leaves it, so gm_query, gm_export, gm_digest,
+ * gm_histogram, gm_tier_counts, gm_verify and gm_poke answer for the loaded table.
+ * *root_record is the stored record of the root, or 0xFFFF when the root is not among the keys
+ * (allowed; gm_verify then reports root_ok = 0).  gm_stats: engine, n_positions, n_stored,
+ * n_tiers, table_bytes; solve_ms is the wall time of the import; forward_ms, backward_ms,
+ * n_edges and algo_bytes are 0, world is 1.
+ * The engine is the one a one-GPU gm_solve of the context would choose: the sparse engine (with
+ * GM_OPT_SYMMETRY as in a solve from this root: canon(key) is stored once per orbit, and every
+ * member of an orbit must be given, with one record; GM_OPT_SYMMETRY 0 stores the keys as
+ * given), tic-tac-toe's record table, the SUBTRACT block engine's byte table (1-byte codes: WIN
+ * / LOSS with remoteness <= 126, slots outside the keys 0), and for 3-word keys (Othello 8x8)
+ * the hash-sharded engine as one rank.  gm_export afterwards returns the imported pairs, sorted.
+ * Every refusal leaves the context without a table (GM_E_STATE from the readers until the next
+ * successful solve or import), and gm_last_error names one offending key in hex words:
+ *   GM_E_GAME  a GM_GAME_GRAPH context (its keys are the host walk's numbering); SUBTRACT at 8
+ *              heaps on the box engine (set GM_OPT_SUB_INTERLEAVE 10);
+ *   GM_E_ARG   a multi-process context, GM_OPT_VIRTUAL_RANKS > 1, GM_ENGINE_DIST_SPARSE on a
+ *              one-word context; n == 0 or a NULL pointer; a record that is 0xFFFF, DRAW, or
+ *              beyond the engine's table; a key given twice; under a symmetry reduction, orbit
+ *              members with different records or an incomplete orbit;
+ *   GM_E_KEY   the root or a key is not a valid position, a key lies in a tier above the root's
+ *              or (dense) outside the root's region;
+ *   GM_E_CAP   keys more than 1,023 tiers below the root.
+ * What the records say is not judged here: gm_verify does that.
+ * This completes the table interface of the reference, whose CacheDict both writes and reads
+ * its per-rank tables (src/cache_dict.py:38-79, opened at src/new_process.py:76-78); a solve
+ * sharded over processes is verified by importing its ranks' exported shares into one context. */
+int gm_import(gm_ctx *ctx, const uint64_t *root_words, const uint64_t *key_words, const uint16_t *records,
+              uint64_t n, uint64_t *n_positions, uint16_t *root_record);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

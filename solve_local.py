@@ -2,7 +2,7 @@
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
     python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
-                          [--loopy]
+                          [--loopy] [--load DIR]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -16,7 +16,11 @@ solved table against the game rules (gm_verify, gamesmanmpi_amd/verify.py: one l
 offending positions; the exit status is non-zero when the table is inconsistent).
 ``--loopy`` solves a game in which positions can repeat (explicit graph, GM_OPT_LOOPY): "Draw"
 is then a real answer, ``--remoteness`` prints ``DRAW`` alone for it and ``--analysis`` adds a
-line ``Draw  N`` under its table.
+line ``Draw  N`` under its table.  ``--load DIR`` takes the place of the solve: the
+``DIR/stats/<rank>/table.npz`` files of a ``solver_launcher.py -sd DIR`` run are loaded onto the
+device (gm_import) and everything else answers for that table; refused with exit status 2 together
+with ``--loopy`` or for a plugin solved as an explicit graph, and a table without the root prints
+``root not in table`` on stderr and exits 1.
 """
 import argparse
 import os
@@ -31,7 +35,7 @@ import solver_launcher  # noqa: E402
 MESSAGES = {0: "Winning position", 1: "Losing position", 2: "Tie", 3: "Draw"}
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("game_file")
     p.add_argument("--custom")
@@ -42,13 +46,39 @@ def main(argv=None):
     p.add_argument("--analysis", action="store_true")
     p.add_argument("--verify", action="store_true")
     p.add_argument("--loopy", action="store_true")
+    p.add_argument("--load", metavar="DIR",
+                   help="in place of the solve, load the table.npz files a solver_launcher.py -sd DIR run wrote")
     p.add_argument("--device", type=int, default=-1)
-    args = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     args.engine = "auto"
+    if args.load and args.loopy:
+        print("--load and --loopy exclude each other: a stored table loads into a descriptor game, a loopy solve is "
+              "an explicit graph", file=sys.stderr)
+        return 2
     game, root = solver_launcher.prepare_game(args)
-    from gamesmanmpi_amd import Solver
+    from gamesmanmpi_amd import Solver, _lib
     s = Solver(game, root, device=args.device, loopy=True) if args.loopy else Solver(game, root, device=args.device)
-    s.solve()
+    if args.load:
+        if s.codec.game_id == _lib.GAME_GRAPH:
+            print("--load needs a game with a device descriptor: %s is solved as an explicit graph, whose keys a "
+                  "stored table does not carry" % args.game_file, file=sys.stderr)
+            s.close()
+            return 2
+        try:
+            s.load_statsdir(args.load)
+            refused = None
+        except _lib.GMError as e:   # a table gm_import refuses (a key twice, orbit mates that disagree, ...)
+            refused = "--load %s: %s" % (args.load, e)
+        if refused or s.value is None:
+            print(refused or "root not in table", file=sys.stderr)
+            s.close()
+            return 1
+    else:
+        s.solve()
     print(MESSAGES[s.value])
     if args.remoteness:
         print(s.root_line())

@@ -43,7 +43,15 @@ Differences, on purpose:
   host and solved as an explicit graph with cycles allowed (GM_OPT_LOOPY, one process); a
   position neither side can decide is a draw, the root line of a drawn root is ``DRAW``
   alone, ``--analysis`` adds a line ``Draw  N`` under its table and ``analysis.json`` a key
-  ``"draw"``.
+  ``"draw"``;
+* ``--load DIR`` takes the place of the solve: every ``DIR/stats/<rank>/table.npz`` (what ``-sd``
+  wrote, one share per rank of a sharded solve) is loaded onto the device (gm_import), the root
+  line is printed from the stored root record, and ``--analysis``, ``--verify``, ``--stats`` and
+  ``-sd`` behave as after a solve -- which is how a solve sharded over processes is verified.
+  A table without the root prints ``root not in table`` on stderr and exits 1.  Refused (exit
+  status 2, one line on stderr) together with ``--loopy``, for a plugin solved as an explicit
+  graph, and when the ranks would shard (one GPU per rank); ranks that share rank 0's GPU let
+  rank 0 load.
 """
 import argparse
 import cProfile
@@ -83,6 +91,8 @@ def build_parser():
                    help="after the root line, check the solved table against the game rules on the device")
     p.add_argument("--loopy", action="store_true",
                    help="solve a game with cycles: explicit graph, undecidable positions are DRAW")
+    p.add_argument("--load", metavar="DIR",
+                   help="in place of the solve, load the table.npz files a run with -sd DIR wrote")
     p.add_argument("--sd-format", choices=("auto", "npz", "reference", "both"), default="auto",
                    help="-sd output: npz table, the reference's shelve layout, or both (auto: both up to "
                         "%d positions, else npz)" % SHELVE_AUTO_LIMIT)
@@ -167,6 +177,10 @@ def rank_plan(world, local_world, n_devices):
 
 def run(args, out=sys.stdout):
     rank, world, local = dist_env()
+    if getattr(args, "load", None) and getattr(args, "loopy", False):
+        print("--load and --loopy exclude each other: a stored table loads into a descriptor game, a loopy solve is "
+              "an explicit graph", file=sys.stderr)
+        return 2
     if args.debug:
         os.makedirs("logs", exist_ok=True)
         logging.basicConfig(filename="logs/proc%d" % rank, level=logging.DEBUG)
@@ -185,6 +199,11 @@ def run(args, out=sys.stdout):
                 print("--verify needs the whole table in one process: this solve is sharded over %d processes, and "
                       "a rank does not hold the tables of its children's owners.  Run it on one process (virtual "
                       "ranks included)." % world, file=sys.stderr)
+            return 2
+        if plan == "sharded" and getattr(args, "load", None):
+            if rank == 0:
+                print("--load builds the whole table in one process: run it on one process, or with more ranks than "
+                      "GPUs (rank 0 then loads)", file=sys.stderr)
             return 2
         if plan == "single" and rank != 0:
             # rank 0 solves for every rank and prints the root line; wait for it by polling
@@ -211,13 +230,35 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
         raise SystemExit("--loopy solves in one process: the graph engine is not sharded")
     solver = Solver(game, root, device=device, engine=engine, loopy=True) if loopy else \
         Solver(game, root, device=device, engine=engine)
+    load = getattr(args, "load", None)
+    if load and solver.codec.game_id == _lib.GAME_GRAPH:
+        print("--load needs a game with a device descriptor: %s is solved as an explicit graph, whose keys a stored "
+              "table does not carry" % args.game_file, file=sys.stderr)
+        solver.close()
+        if plan == "single":
+            dist.release_waiters(world, ok=False)
+        return 2
     if plan == "sharded":
         dist.join(solver.ctx, rank, world)
+    elif load:
+        pass   # one context holds the whole table: no virtual ranks
     elif plan == "single" and solver.codec.game_id != _lib.GAME_GRAPH and world <= MAX_VIRTUAL_RANKS:
         # the sharded algorithm over `world` loopback ranks on this one GPU
         solver.ctx.set_option(_lib.OPT_VIRTUAL_RANKS, world)
     logging.debug("solving %s from %r on device %s", args.game_file, root, device)
-    if args.cp:
+    if load:
+        try:
+            solver.load_statsdir(load)
+            refused = None
+        except _lib.GMError as e:   # a table gm_import refuses (a key twice, orbit mates that disagree, ...)
+            refused = "--load %s: %s" % (load, e)
+        if refused or solver.value is None:
+            print(refused or "root not in table", file=sys.stderr)
+            solver.close()
+            if plan == "single":
+                dist.release_waiters(world, ok=False)
+            return 1
+    elif args.cp:
         prof = cProfile.Profile()
         prof.runcall(solver.solve)
         prof.dump_stats("time")
