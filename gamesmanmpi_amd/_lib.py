@@ -38,6 +38,8 @@ BOXPLAN_COUNTS, BOXPLAN_SRCS, BOXPLAN_DSTS = 11, 12, 13
 BOP_TIER, BOP_PACK, BOP_UNPACK, BOP_SEND, BOP_RECV, BOP_RECORD, BOP_WAIT = range(7)
 BEV_DONE, BEV_PACKED = range(2)
 REC_UNSOLVED = 0xFFFF
+SEL_WIN, SEL_LOSS, SEL_TIE, SEL_DRAW = 1, 2, 4, 8   # gm_select_t.values: 1 << value code
+SEL_ANY_REM = 0x3FFF   # gm_select_t.rem_hi: no upper bound
 
 ERRORS = {
     -1: "GM_E_ARG", -2: "GM_E_GAME", -3: "GM_E_HIP", -4: "GM_E_NOMEM", -5: "GM_E_STATE",
@@ -51,7 +53,7 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
-           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import")
+           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import", "gm_select")
 
 
 class GMError(RuntimeError):
@@ -106,6 +108,16 @@ class Verify(ctypes.Structure):
         return d
 
 
+class Select(ctypes.Structure):
+    """gm_select_t (include/gmsolve.h)."""
+    _fields_ = [
+        ("values", ctypes.c_uint32),
+        ("rem_lo", ctypes.c_uint32),
+        ("rem_hi", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 _lib = None
 
 
@@ -140,6 +152,7 @@ def lib():
         "gm_digest": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "gm_histogram": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int), P(u64)]),
         "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
+        "gm_select": (ctypes.c_int, [vp, P(Select), vp, vp, u64, P(u64)]),
         "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
         "gm_draw_count": (ctypes.c_int, [vp, P(u64)]),
         "gm_import": (ctypes.c_int, [vp, vp, vp, vp, u64, P(u64), P(ctypes.c_uint16)]),

@@ -45,6 +45,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1793,6 +1794,12 @@ static int dense_box_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
+// gm_select over the same boxes (select_common.hpp)
+static int dense_box_select(Ctx *c, const SelectDev &s) {
+    DenseBox *d = c->dbox;
+    return byte_select_launch<1>(c, s, d->table, d->d_boxes, d->boxes.size(), 12, 8);
+}
+
 static int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
     *p = c->dbox->table;
     *bytes = 1ull << 32;
@@ -1833,7 +1840,7 @@ static void dense_box_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
-                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_table, dense_box_free,
+                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_select, dense_box_table, dense_box_free,
                  dense_box_verify, dense_box_poke)
 
 }  // namespace gm

@@ -35,6 +35,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -1242,6 +1243,12 @@ static int dense_sub_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
+// gm_select over the root's region, one unit of 16^heaps bytes (select_common.hpp)
+static int dense_sub_select(Ctx *c, const SelectDev &s) {
+    DenseSub *d = c->dsub;
+    return byte_select_launch<0>(c, s, d->table, nullptr, 1, 4 * d->heaps, d->heaps);
+}
+
 static int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {
     DenseSub *d = c->dsub;
     *p = d->table;
@@ -1374,7 +1381,7 @@ static int dense_sub_import(Ctx *c, const void *keys_, const uint16_t *recs, uin
 }
 
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
-                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_table, dense_sub_free,
+                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_select, dense_sub_table, dense_sub_free,
                  dense_sub_verify, dense_sub_poke, dense_sub_import)
 
 }  // namespace gm

@@ -45,6 +45,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1494,6 +1495,14 @@ static int dist_box_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
+// gm_select over the same boxes (select_common.hpp)
+static int dist_box_select(Ctx *c, const SelectDev &s) {
+    DistBox *d = c->dist_box;
+    for (auto &R : d->ranks)
+        if (R.table) GM_TRY(byte_select_launch<1>(c, s, R.table, R.d_boxes, R.boxes.size(), 12, 8));
+    return GM_OK;
+}
+
 // gm_verify over every virtual rank's own boxes; each code, a position's own and its children's,
 // is read from its box's holder as box_launch_query reads it (d_owner, d_tables)
 static int dist_box_verify(Ctx *c, const VerifyDev &v) {
@@ -1687,7 +1696,7 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
 }
 
 GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
-                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_table, dist_box_free,
+                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_select, dist_box_table, dist_box_free,
                  dist_box_verify, dist_box_poke)
 
 }  // namespace gm

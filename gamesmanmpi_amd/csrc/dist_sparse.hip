@@ -1306,6 +1306,12 @@ static int dist_sparse_histogram(Ctx *c, Hist *out) {
     });
 }
 
+static int dist_sparse_select(Ctx *c, const SelectDev &s) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        return tiers_select(c, desc, rank_tiers<key_t<std::decay_t<decltype(desc)>>>(c), s);
+    });
+}
+
 // a key is stored by its owner rank: one group of tables per rank
 template <class D>
 static int query_ranks(Ctx *c, const D &desc, const key_t<D> *keys, uint16_t *recs, uint64_t n) {
@@ -1406,7 +1412,7 @@ static int dist_sparse_import(Ctx *c, const void *keys, const uint16_t *recs, ui
 }
 
 GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
-                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, nullptr, dist_sparse_free,
+                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, dist_sparse_select, nullptr, dist_sparse_free,
                  dist_sparse_verify, dist_sparse_poke, dist_sparse_import)
 
 }  // namespace gm

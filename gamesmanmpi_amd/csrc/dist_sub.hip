@@ -62,6 +62,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 #include <mutex>
 
@@ -770,6 +771,14 @@ static int dist_sub_histogram(Ctx *c, Hist *out) {
     return rc != GM_OK ? rc : rc2;
 }
 
+// gm_select over the same blocks (select_common.hpp)
+static int dist_sub_select(Ctx *c, const SelectDev &s) {
+    DistSub *d = c->dist_sub;
+    for (auto &R : d->ranks)
+        if (R.off.back()) GM_TRY(byte_select_launch<0>(c, s, R.table, R.dlist, R.off.back(), 4 * d->low, d->heaps));
+    return GM_OK;
+}
+
 static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     DistSub *d = c->dist_sub;
     hipStream_t H = c->stream;
@@ -976,7 +985,7 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
 }
 
 GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
-                 dist_sub_query, dist_sub_digest, dist_sub_histogram, nullptr, dist_sub_free,
+                 dist_sub_query, dist_sub_digest, dist_sub_histogram, dist_sub_select, nullptr, dist_sub_free,
                  dist_sub_verify, dist_sub_poke)
 
 }  // namespace gm

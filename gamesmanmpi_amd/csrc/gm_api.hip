@@ -2,6 +2,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 #include <chrono>
 #include <stdlib.h>
@@ -828,6 +829,65 @@ int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap
     });
     for (uint64_t i = 0; i < n; i++)
         for (int j = 0; j < W; j++) bad_key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
+    return GM_OK;
+}
+
+int gm_select(gm_ctx *h, const gm_select_t *what, uint64_t *key_words, uint16_t *records, uint64_t cap, uint64_t *n) {
+    if (!h || !what || !n) { set_error("gm_select: a NULL argument"); return GM_E_ARG; }
+    if (!what->values || (what->values & ~15u)) { set_error("gm_select: values is not an OR of GM_SEL_*"); return GM_E_ARG; }
+    if (what->rem_lo > what->rem_hi) { set_error("gm_select: rem_lo exceeds rem_hi"); return GM_E_ARG; }
+    if (what->reserved) { set_error("gm_select: reserved is not 0"); return GM_E_ARG; }
+    GM_TRY(need_solved(h));
+    Ctx *c = &h->c;
+    if (!c->solved_by->select) { set_error("gm_select: this engine's tables are not selected from"); return GM_E_STATE; }
+    GM_HIP(hipSetDevice(c->device));
+    const uint64_t want = key_words ? cap : 0;
+    const uint64_t key_bytes = c->wide ? sizeof(K128) : 8;
+    std::vector<unsigned char> raw;
+    std::vector<uint16_t> rr;
+    uint64_t found = 0;
+    // the list holds SEL_FIRST_CAP pairs at first; when more match and the caller has room for
+    // them, the table is read again into a list of exactly that room
+    for (uint64_t dev_cap = std::min(want, SEL_FIRST_CAP);;) {
+        SelectRun run;
+        GM_TRY(select_begin(c, *what, dev_cap, key_bytes, &run));
+        const int rc = c->solved_by->select(c, run.dev);
+        const int rc2 = select_end(c, &run, &found, &raw, &rr);
+        if (rc != GM_OK) return rc;
+        if (rc2 != GM_OK) return rc2;
+        if (std::min(found, want) <= dev_cap) break;
+        dev_cap = std::min(found, want);
+    }
+    *n = found;
+    if (!want) return GM_OK;
+    const uint64_t m = rr.size();
+    if (!c->wide) {
+        std::vector<std::pair<uint64_t, uint16_t>> out(m);
+        for (uint64_t i = 0; i < m; i++) out[i] = {((const uint64_t *)raw.data())[i], rr[i]};
+        std::sort(out.begin(), out.end());
+        for (uint64_t i = 0; i < m; i++) {
+            key_words[i] = out[i].first;
+            if (records) records[i] = out[i].second;
+        }
+        return GM_OK;
+    }
+    // ascending ABI key order (a wide key: the position string as one integer)
+    const int W = WIDE_WORDS;
+    std::vector<uint64_t> w((size_t)W * m);
+    for (uint64_t i = 0; i < m; i++) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
+    std::vector<uint64_t> idx(m);
+    for (uint64_t i = 0; i < m; i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+        for (int j = W - 1; j >= 0; j--) {
+            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
+            if (x != y) return x < y;
+        }
+        return false;
+    });
+    for (uint64_t i = 0; i < m; i++) {
+        for (int j = 0; j < W; j++) key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
+        if (records) records[i] = rr[idx[i]];
+    }
     return GM_OK;
 }
 

@@ -63,6 +63,7 @@ struct DistSparse;
 struct Graph;
 struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
 struct VerifyDev;   // verify_common.hpp: the device accumulator of gm_verify
+struct SelectDev;   // select_common.hpp: the filter and the device accumulator of gm_select
 struct Engine;
 
 struct Ctx {
@@ -147,7 +148,7 @@ struct Ctx {
 // One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
 // record next to its functions; gm_solve picks one per solve from the context's options
 // (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
-// of the solved table (export, query, digest, histogram, verify, dense table, rank stats) goes through it.
+// of the solved table (export, query, digest, histogram, select, verify, dense table, rank stats) goes through it.
 struct Engine {
     int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
     int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
@@ -155,6 +156,7 @@ struct Engine {
     int (*query)(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
     int (*digest)(Ctx *c, uint64_t *digest, uint64_t *n);
     int (*histogram)(Ctx *c, Hist *out);
+    int (*select)(Ctx *c, const SelectDev &s);         // gm_select: every matching position into the accumulator
     int (*table)(Ctx *c, void **p, uint64_t *bytes);   // null: the engine has no dense table
     void (*free_)(Ctx *c);
     int (*verify)(Ctx *c, const VerifyDev &v);         // gm_verify: every stored position into the accumulator

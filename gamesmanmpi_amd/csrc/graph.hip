@@ -18,6 +18,7 @@
 #include "graph_common.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 #include <algorithm>
 
@@ -215,6 +216,26 @@ static int graph_histogram(Ctx *c, Hist *out) {
     return GM_OK;
 }
 
+// gm_select over the nodes (select_common.hpp): a node's key is its index, its record
+// graph_record of its score, so a loopy table's DRAW is selectable
+__global__ __launch_bounds__(256) void graph_select_kernel(const uint16_t *__restrict__ score, uint64_t n, SelectDev s) {
+    SelectTally t;
+    // per wave, so that every lane makes the same trips
+    for (uint64_t w0 = blockIdx.x * 256ull + (threadIdx.x & ~63u); w0 < n; w0 += (uint64_t)gridDim.x * 256ull) {
+        const uint64_t i = w0 + (threadIdx.x & 63u);
+        const uint16_t rec = i < n ? graph_record(score[i]) : REC_UNSOLVED;
+        select_note(s, t, select_match(s.values, s.rem_lo, s.rem_hi, rec), i, rec);
+    }
+    select_flush(s, t);
+}
+
+static int graph_select(Ctx *c, const SelectDev &s) {
+    Graph *g = c->graph;
+    hipLaunchKernelGGL(graph_select_kernel, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, g->score, g->n, s);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
 // gm_verify over the nodes (verify_common.hpp): a node's score against its primitive() code or
 // the best of its children's scores, read through the CSR the solve left on the device.  A
 // node's key is its index, so no key or placement class exists here.
@@ -288,6 +309,6 @@ void graph_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(graph_engine, GM_ENGINE_GRAPH, nullptr, graph_export,
-                 graph_query, graph_digest, graph_histogram, nullptr, graph_free, graph_verify, graph_poke)
+                 graph_query, graph_digest, graph_histogram, graph_select, nullptr, graph_free, graph_verify, graph_poke)
 
 }  // namespace gm

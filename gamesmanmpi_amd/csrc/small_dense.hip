@@ -9,6 +9,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 namespace gm {
 
@@ -148,6 +149,27 @@ static int small_dense_histogram(Ctx *c, Hist *out) {
     return GM_OK;
 }
 
+// gm_select over the host records gm_query answers from: the matches go into the accumulator
+// and the first s.cap of them into the list (select_common.hpp)
+static int small_dense_select(Ctx *c, const SelectDev &s) {
+    SmallDense *sd = c->sd;
+    std::vector<uint64_t> keys;
+    std::vector<uint16_t> recs;
+    uint64_t acc[SEL_WORDS] = {0, 0};
+    for (uint32_t i = 0; i < sd->slots; i++) {
+        if (!select_match(s.values, s.rem_lo, s.rem_hi, sd->h_rec[i])) continue;
+        if (acc[0]++ < s.cap) { keys.push_back(i); recs.push_back(sd->h_rec[i]); }
+    }
+    acc[1] = acc[0];
+    GM_HIP(hipMemcpyAsync(s.acc, acc, sizeof acc, hipMemcpyHostToDevice, c->stream));
+    if (!keys.empty()) {
+        GM_HIP(hipMemcpyAsync(s.keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, c->stream));
+        GM_HIP(hipMemcpyAsync(s.recs, recs.data(), recs.size() * 2, hipMemcpyHostToDevice, c->stream));
+    }
+    GM_HIP(hipStreamSynchronize(c->stream));   // the vectors leave scope
+    return GM_OK;
+}
+
 // gm_verify over the record table (verify_common.hpp): the reachable slots (record != 0xFFFF)
 // are the stored positions; slot = key, so no key or placement class exists here
 template <class D>
@@ -250,7 +272,7 @@ static int small_dense_import(Ctx *c, const void *keys_, const uint16_t *recs, u
 }
 
 GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
-                 small_dense_query, small_dense_digest, small_dense_histogram, nullptr, small_dense_free,
+                 small_dense_query, small_dense_digest, small_dense_histogram, small_dense_select, nullptr, small_dense_free,
                  small_dense_verify, small_dense_poke, small_dense_import)
 
 }  // namespace gm

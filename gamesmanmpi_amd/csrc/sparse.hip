@@ -844,6 +844,10 @@ static int sparse_histogram(Ctx *c, Hist *out) {
     });
 }
 
+static int sparse_select(Ctx *c, const SelectDev &s) {
+    return with_desc(c, [&](const auto &d) { return tiers_select(c, d, tier_list(c->sp), s); });
+}
+
 static int sparse_verify(Ctx *c, const VerifyDev &v) {
     return with_desc(c, [&](const auto &d) {
         return tiers_verify(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, v);
@@ -886,7 +890,7 @@ static int sparse_import(Ctx *c, const void *keys, const uint16_t *recs, uint64_
 }
 
 GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
-                 sparse_query, sparse_digest, sparse_histogram, nullptr, sparse_free, sparse_verify, sparse_poke,
+                 sparse_query, sparse_digest, sparse_histogram, sparse_select, nullptr, sparse_free, sparse_verify, sparse_poke,
                  sparse_import)
 
 }  // namespace gm

@@ -17,6 +17,7 @@
 #pragma once
 #include "sparse_common.hpp"
 #include "verify_common.hpp"
+#include "select_common.hpp"
 
 namespace gm {
 
@@ -478,6 +479,26 @@ __global__ void res_hist_kernel(D d, const typename KT<key_t<D>>::Slot *__restri
     score_bins_flush(lds, bins, nbin);
 }
 
+// gm_select over a tier table (select_common.hpp): every matching representative emits each
+// member of its orbit with the representative's record, as res_gather_kernel does.  The loop
+// runs per wave; the orbit walks diverge, which select_note allows.
+template <class D>
+__global__ __launch_bounds__(256) void res_select_kernel(D d, const typename KT<key_t<D>>::Slot *__restrict__ sl,
+                                                         uint64_t cap, SelectDev s) {
+    using K = key_t<D>;
+    SelectTally t;
+    for (uint64_t w0 = blockIdx.x * 256ull + (threadIdx.x & ~63u); w0 < cap; w0 += (uint64_t)gridDim.x * 256ull) {
+        const uint64_t i = w0 + (threadIdx.x & 63u);
+        if (i >= cap) continue;
+        const K key = slot_key(sl[i]);
+        if (key_empty(key)) continue;
+        const uint16_t rec = record_of_score((uint16_t)slot_score(sl[i]));
+        if (!select_match(s.values, s.rem_lo, s.rem_hi, rec)) continue;
+        d.orbit(key, [&](const K &k) { select_note(s, t, true, k, rec); });
+    }
+    select_flush(s, t);
+}
+
 // gm_verify over one tier table (verify_common.hpp): table `t` of group `g` of the G x ntabs
 // matrix `tabs` (row = owner rank, one row for the one-GPU engine; column = tier from the
 // root's, t_root).  Every occupied slot: its key (valid, its own representative, of this tier
@@ -740,6 +761,17 @@ inline int tiers_histogram(Ctx *c, const D &d, const TierList<key_t<D>> &tiers, 
             hipLaunchKernelGGL(res_hist_kernel<D>, dim3(grid_counted(T->cap)), dim3(256), b.lds_bytes, c->stream, d,
                                T->slots, T->cap, b.d, b.nbin, b.use_lds);
     return score_bins_end(c, &b, out);
+}
+
+// gm_select over the tables (select_common.hpp)
+template <class D>
+inline int tiers_select(Ctx *c, const D &d, const TierList<key_t<D>> &tiers, const SelectDev &s) {
+    for (auto *T : tiers)
+        if (T->count)
+            hipLaunchKernelGGL(res_select_kernel<D>, dim3(grid_counted(T->cap)), dim3(256), 0, c->stream, d, T->slots,
+                               T->cap, s);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
 }
 
 // One group of tier tables a query looks in: a tier per table from the root's (t_root) on.  A

@@ -199,6 +199,26 @@ class Context:
         n = min(cap, n_bad.value)
         return out.as_dict(), [_lib.words_to_int(keys[i]) for i in range(n)]
 
+    def select(self, values, rem_lo=0, rem_hi=_lib.SEL_ANY_REM, cap=64, as_array=False):
+        """gm_select: the held positions whose value is among `values` (an OR of _lib.SEL_*) and
+        whose remoteness lies in [rem_lo, rem_hi], found on the device.  Returns (n, keys,
+        records): n counts every match, keys are up to `cap` of them ascending -- Python ints, or
+        with as_array the array export() returns (1-D uint64, (m, words) for multi-word keys) --
+        and records their u16 records."""
+        what = _lib.Select(int(values), int(rem_lo), int(rem_hi), 0)
+        n = ctypes.c_uint64()
+        cap = int(cap)
+        keys = np.zeros((max(1, cap), self.words), dtype=np.uint64)
+        recs = np.zeros(max(1, cap), dtype=np.uint16)
+        _lib.check(self.L.gm_select(self.h, ctypes.byref(what), keys.ctypes.data if cap else None,
+                                    recs.ctypes.data if cap else None, cap, ctypes.byref(n)))
+        m = min(cap, n.value)
+        if as_array:
+            return n.value, (keys[:m] if self.words > 1 else keys[:m, 0]), recs[:m]
+        if self.words == 1:
+            return n.value, [int(k) for k in keys[:m, 0]], recs[:m]
+        return n.value, [_lib.words_to_int(keys[i]) for i in range(m)], recs[:m]
+
     def poke(self, key, record):
         """gm_poke (test hook): overwrite one held position's record; 0xFFFF removes it."""
         w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
@@ -420,6 +440,61 @@ class Solver:
                 labels = list(range(len(kids)))
         rows = [(m, self.codec.pos(k)) + split_record(r) for m, k, r in zip(labels, kids, recs)]
         return rows, (rows[best] if best is not None else None)
+
+    def find(self, spec_or_values, rem=None, cap=16, with_keys=False):
+        """The positions with a given value and remoteness, selected on the device (gm_select).
+        `spec_or_values` is a spec of gamesmanmpi_amd/find.py ("tie:9", "win,loss:2-5",
+        "win:max") or an OR of _lib.SEL_* with `rem` None (any), one remoteness or (lo, hi).
+        Returns (n, [(position, value, remoteness), ...]): n counts every match, the rows are
+        up to `cap` of them ascending by key.  The nodes of a graph solve with symmetry
+        generators are orbit representatives: they are expanded here with codec.members and
+        every member counts, as in analysis()."""
+        from . import find
+        if isinstance(spec_or_values, (str, find.Spec)):
+            spec = find.as_spec(spec_or_values)
+            if spec.want_max:
+                spec = find.resolve(spec, self.analysis())
+        else:
+            lo, hi = (0, find.ANY) if rem is None else (rem if isinstance(rem, (tuple, list)) else (rem, rem))
+            spec = find.Spec(int(spec_or_values), int(lo), int(hi), False)
+        if self.codec.game_id == _lib.GAME_GRAPH and self.codec.gens:
+            n_rep = self.ctx.select(spec.values, spec.rem_lo, spec.rem_hi, 0)[0]
+            _, keys, recs = self.ctx.select(spec.values, spec.rem_lo, spec.rem_hi, n_rep)
+            n, rows, kept = 0, [], []
+            for k, r in zip(keys, recs):
+                members = self.codec.members(k)
+                n += len(members)
+                for p in members[:max(0, cap - len(rows))]:
+                    rows.append((p,) + split_record(r))
+                    kept.append(k)
+        else:
+            n, kept, recs = self.ctx.select(spec.values, spec.rem_lo, spec.rem_hi, cap)
+            rows = [(self.codec.pos(k),) + split_record(r) for k, r in zip(kept, recs)]
+        return (n, rows, kept) if with_keys else (n, rows)
+
+    def line(self, pos=None, max_plies=0x4000):
+        """The principal variation from `pos` (default the root): rows (move, position, value,
+        remoteness), the first with move None, each next one the row moves() marks as the
+        solver's choice, the last a primitive position.  From a DRAW position of a loopy solve
+        nobody ends the game: the line stops on the first position it repeats, or after
+        `max_plies` moves."""
+        pos = self.root if pos is None else pos
+        rows, seen, move = [], set(), None
+        while True:
+            v, r = self.lookup(pos)
+            rows.append((move, pos, v, r))
+            if self.module.primitive(pos) != UNDECIDED or len(rows) > max_plies:
+                break
+            if v == DRAW:
+                k = self.codec.key(pos)
+                if k in seen:
+                    break
+                seen.add(k)
+            _, best = self.moves(pos)
+            if best is None:
+                break
+            move, pos = best[0], best[1]
+        return rows
 
     def close(self):
         self.ctx.close()

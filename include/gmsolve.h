@@ -425,6 +425,44 @@ int gm_poke(gm_ctx *ctx, const uint64_t *key_words, uint16_t record);
 int gm_import(gm_ctx *ctx, const uint64_t *root_words, const uint64_t *key_words, const uint16_t *records,
               uint64_t n, uint64_t *n_positions, uint16_t *root_record);
 
+/* What gm_select looks for: the values wanted (1 << value code, the codes of src/utils.py:4 and
+ * 3 for DRAW) and an inclusive remoteness range. */
+enum { GM_SEL_WIN = 1, GM_SEL_LOSS = 2, GM_SEL_TIE = 4, GM_SEL_DRAW = 8 };
+typedef struct {
+    uint32_t values;    /* OR of GM_SEL_*: the values wanted */
+    uint32_t rem_lo;    /* remoteness range, inclusive */
+    uint32_t rem_hi;    /* >= 0x3FFF: no upper bound */
+    uint32_t reserved;  /* 0 */
+} gm_select_t;          /* 16 bytes */
+
+/* The positions of this rank's solved table that have a wanted value and a remoteness in range,
+ * found on the device in one streaming pass over the table (the census pass of gm_histogram with
+ * a predicate and a compacted output; no export, no host filter).
+ * *n = the matches among exactly the positions gm_histogram counts for this context (the root's
+ * region of the dense tables; every member of a stored representative's symmetry orbit; all
+ * virtual ranks; in a multi-process solve the keys this rank holds, so the ranks' results
+ * partition the one-GPU result).  For one value and rem_lo == rem_hi == r, *n is counts[v][r] of
+ * gm_histogram.  GM_SEL_DRAW matches record 0xC000 (remoteness 0) of a loopy graph solve; on a
+ * table without DRAW it matches nothing and is no error.
+ * The records judged are the ones gm_query returns (after gm_poke or gm_import the selection
+ * follows the table); a slot without a record -- a dense code 0 inside the region, an unscored
+ * sparse slot -- matches nothing.  What the records say is not judged here: gm_verify does that.
+ * Up to cap matches are written: keys to key_words, gm_key_words() words each, in gm_export /
+ * gm_export_key order (ascending); their records to records, which may be NULL.  All of them
+ * when *n <= cap, else any cap of them, still ascending and distinct (gm_verify's convention
+ * for its offender list).  key_words == NULL or cap == 0: the count only.  Nothing but the count
+ * and at most cap pairs leaves the device: the first pass keeps up to 65,536 pairs, and a second
+ * pass with room for min(*n, cap) runs only when that is more.  Places in the list are reserved
+ * per wave (one atomic for a wave's matches), and a wave that finds the list full only counts,
+ * so a filter that matches everything costs a census, not an export.
+ * GM_E_ARG (checked first): what or n is NULL, values is 0 or has a bit above GM_SEL_DRAW,
+ * rem_lo > rem_hi, reserved != 0.  GM_E_STATE before a solve and after a failed solve or import.
+ * One-word and multi-word key contexts alike.
+ * Replaces reopening the `resolved` / `remote` shelves and scanning them on the host
+ * (src/cache_dict.py:38-79), the reference's only way to name the positions behind a statistic. */
+int gm_select(gm_ctx *ctx, const gm_select_t *what, uint64_t *key_words, uint16_t *records, uint64_t cap,
+              uint64_t *n);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

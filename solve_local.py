@@ -2,7 +2,7 @@
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
     python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
-                          [--loopy] [--load DIR]
+                          [--loopy] [--load DIR] [--find SPEC ...] [--find-cap N] [--line]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -14,6 +14,10 @@ intends for the root's canonical value, computed on the GPU by libgmsolve.so;
 positions by value and remoteness (gamesmanmpi_amd/analysis.py), ``--verify`` the check of the
 solved table against the game rules (gm_verify, gamesmanmpi_amd/verify.py: one line, then any
 offending positions; the exit status is non-zero when the table is inconsistent).
+``--find SPEC`` (repeatable) prints ``Found N positions: SPEC`` and up to ``--find-cap`` (16)
+positions with that value and remoteness, selected on the device (gm_select,
+gamesmanmpi_amd/find.py; a bad spec exits 2 before the solve), and ``--line`` the principal
+variation from the root, one row per ply.
 ``--loopy`` solves a game in which positions can repeat (explicit graph, GM_OPT_LOOPY): "Draw"
 is then a real answer, ``--remoteness`` prints ``DRAW`` alone for it and ``--analysis`` adds a
 line ``Draw  N`` under its table.  ``--load DIR`` takes the place of the solve: the
@@ -45,6 +49,10 @@ def build_parser():
     p.add_argument("--remoteness", action="store_true")
     p.add_argument("--analysis", action="store_true")
     p.add_argument("--verify", action="store_true")
+    p.add_argument("--find", action="append", metavar="SPEC", default=[],
+                   help="name the positions with a value and remoteness: VALUE[,VALUE...][:R | :LO-HI | :max]")
+    p.add_argument("--find-cap", type=int, default=16, metavar="N")
+    p.add_argument("--line", action="store_true", help="print the principal variation from the root")
     p.add_argument("--loopy", action="store_true")
     p.add_argument("--load", metavar="DIR",
                    help="in place of the solve, load the table.npz files a solver_launcher.py -sd DIR run wrote")
@@ -58,6 +66,11 @@ def main(argv=None):
     if args.load and args.loopy:
         print("--load and --loopy exclude each other: a stored table loads into a descriptor game, a loopy solve is "
               "an explicit graph", file=sys.stderr)
+        return 2
+    try:
+        specs = solver_launcher.find_specs(args)
+    except ValueError as e:
+        print("--find: %s" % e, file=sys.stderr)
         return 2
     game, root = solver_launcher.prepare_game(args)
     from gamesmanmpi_amd import Solver, _lib
@@ -87,6 +100,11 @@ def main(argv=None):
         print(analysis.format_table(s.analysis()))
         if args.loopy:
             print("Draw  %d" % s.draw_count())
+    if specs:
+        from gamesmanmpi_amd import find
+        find.report(s, specs, max(0, args.find_cap), sys.stdout)
+    if args.line:
+        solver_launcher.write_line(s, sys.stdout)
     status = 0
     if args.verify:
         from gamesmanmpi_amd import verify

@@ -39,6 +39,16 @@ Differences, on purpose:
   writes ``DIR/stats/verify.json``.  Ranks that share one solve on rank 0 verify as one
   process does; a solve sharded over processes is refused before it starts, since no rank
   holds the tables of its children's owners;
+* ``--find SPEC`` (repeatable) names the positions behind a statistic: after the root line (and
+  the ``--analysis`` table) it prints ``Found N positions: SPEC`` and up to ``--find-cap`` (16)
+  positions with their records, ascending by key, selected on the device (gm_select,
+  gamesmanmpi_amd/find.py).  SPEC is ``VALUE[,VALUE...][:R | :LO-HI | :max]`` with values win,
+  loss, tie, draw; a bad spec exits 2 before the solve.  Sharded ranks each select among their
+  own keys and rank 0 prints the merged result; with ``-sd DIR`` rank 0 writes
+  ``DIR/stats/find.json``;
+* ``--line`` prints ``Line:`` and the principal variation from the root, one row per ply
+  (``  K. <move> -> <position>: TIE in 8``); like ``--verify`` it needs the whole table in one
+  process and is refused (exit status 2) when the solve is sharded over processes;
 * ``--loopy`` is for games in which a position can repeat: the plugin is enumerated on the
   host and solved as an explicit graph with cycles allowed (GM_OPT_LOOPY, one process); a
   position neither side can decide is a draw, the root line of a drawn root is ``DRAW``
@@ -89,6 +99,11 @@ def build_parser():
                    help="after the root line, print the positions by value and remoteness")
     p.add_argument("--verify", action="store_true",
                    help="after the root line, check the solved table against the game rules on the device")
+    p.add_argument("--find", action="append", metavar="SPEC", default=[],
+                   help="after the root line, name the positions with a value and remoteness: "
+                        "VALUE[,VALUE...][:R | :LO-HI | :max] (repeatable)")
+    p.add_argument("--find-cap", type=int, default=16, metavar="N", help="positions printed per --find (default 16)")
+    p.add_argument("--line", action="store_true", help="after the root line, print the principal variation from the root")
     p.add_argument("--loopy", action="store_true",
                    help="solve a game with cycles: explicit graph, undecidable positions are DRAW")
     p.add_argument("--load", metavar="DIR",
@@ -181,6 +196,11 @@ def run(args, out=sys.stdout):
         print("--load and --loopy exclude each other: a stored table loads into a descriptor game, a loopy solve is "
               "an explicit graph", file=sys.stderr)
         return 2
+    try:
+        find_specs(args)
+    except ValueError as e:
+        print("--find: %s" % e, file=sys.stderr)
+        return 2
     if args.debug:
         os.makedirs("logs", exist_ok=True)
         logging.basicConfig(filename="logs/proc%d" % rank, level=logging.DEBUG)
@@ -199,6 +219,11 @@ def run(args, out=sys.stdout):
                 print("--verify needs the whole table in one process: this solve is sharded over %d processes, and "
                       "a rank does not hold the tables of its children's owners.  Run it on one process (virtual "
                       "ranks included)." % world, file=sys.stderr)
+            return 2
+        if plan == "sharded" and getattr(args, "line", False):
+            if rank == 0:
+                print("--line needs the whole table in one process: this solve is sharded over %d processes.  Run it "
+                      "on one process (virtual ranks included)." % world, file=sys.stderr)
             return 2
         if plan == "sharded" and getattr(args, "load", None):
             if rank == 0:
@@ -269,6 +294,12 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
         out.flush()
     if getattr(args, "analysis", False):
         report_analysis(args, solver, rank, world, plan, out)
+    if find_specs(args):
+        from gamesmanmpi_amd import find
+        find.report(solver, find_specs(args), max(0, args.find_cap), out, args.statsdir, rank, world,
+                    sharded=plan == "sharded")
+    if getattr(args, "line", False) and rank == 0:
+        write_line(solver, out)
     status = 0
     if getattr(args, "verify", False) and rank == 0:
         from gamesmanmpi_amd import verify
@@ -283,6 +314,25 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     if plan == "single":
         dist.release_waiters(world)
     return status
+
+
+def find_specs(args):
+    """The parsed --find specs (ValueError, with the parser's message, for a bad one)."""
+    texts = getattr(args, "find", None) or []
+    if not texts:
+        return []
+    from gamesmanmpi_amd import find
+    return [find.parse_spec(t) for t in texts]
+
+
+def write_line(solver, out):
+    """--line: the principal variation from the root, one row per ply."""
+    from gamesmanmpi_amd.verify import _record_text
+    out.write("Line:\n")
+    for ply, (move, pos, value, remoteness) in enumerate(solver.line()):
+        step = "" if move is None else "%r -> " % (move,)
+        out.write("  %d. %s%r: %s\n" % (ply, step, pos, _record_text(value, remoteness)))
+    out.flush()
 
 
 def report_analysis(args, solver, rank, world, plan, out):
