@@ -53,7 +53,8 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_tier_counts", "gm_adopt_buffer", "gm_dense_table", "gm_dist_plan", "gm_box_plan",
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
-           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import", "gm_select")
+           "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import", "gm_select",
+           "gm_moves")
 
 
 class GMError(RuntimeError):
@@ -118,6 +119,24 @@ class Select(ctypes.Structure):
     ]
 
 
+class Moves(ctypes.Structure):
+    """gm_moves_t (include/gmsolve.h): one key's answer from gm_moves."""
+    _fields_ = [
+        ("first", ctypes.c_uint64),
+        ("count", ctypes.c_uint16),
+        ("best", ctypes.c_int16),
+        ("record", ctypes.c_uint16),
+        ("n_best", ctypes.c_uint16),
+    ]
+
+
+def moves_dtype():
+    """The numpy dtype of an array of gm_moves_t."""
+    import numpy as np
+    return np.dtype([("first", np.uint64), ("count", np.uint16), ("best", np.int16), ("record", np.uint16),
+                     ("n_best", np.uint16)])
+
+
 _lib = None
 
 
@@ -153,6 +172,7 @@ def lib():
         "gm_histogram": (ctypes.c_int, [vp, vp, ctypes.c_int, P(ctypes.c_int), P(u64)]),
         "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
         "gm_select": (ctypes.c_int, [vp, P(Select), vp, vp, u64, P(u64)]),
+        "gm_moves": (ctypes.c_int, [vp, vp, u64, vp, vp, vp, u64, P(u64)]),
         "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
         "gm_draw_count": (ctypes.c_int, [vp, P(u64)]),
         "gm_import": (ctypes.c_int, [vp, vp, vp, vp, u64, P(u64), P(ctypes.c_uint16)]),

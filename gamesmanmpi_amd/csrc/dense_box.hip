@@ -45,6 +45,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
@@ -1806,6 +1807,12 @@ static int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
     return GM_OK;
 }
 
+// gm_moves: every code at box_index_of_key of its key (moves_common.hpp)
+static int dense_box_moves(Ctx *c, const MovesReq &r) {
+    DenseBox *d = c->dbox;
+    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<1>(c, mv, d->d_tables, nullptr, 0, 8); });
+}
+
 // gm_verify over the region's boxes, each 4 KiB of the table (verify_common.hpp)
 static int dense_box_verify(Ctx *c, const VerifyDev &v) {
     DenseBox *d = c->dbox;
@@ -1841,6 +1848,6 @@ static void dense_box_free(Ctx *c) {
 
 GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
                  dense_box_query, dense_box_digest, dense_box_histogram, dense_box_select, dense_box_table, dense_box_free,
-                 dense_box_verify, dense_box_poke)
+                 dense_box_verify, dense_box_poke, nullptr, dense_box_moves)
 
 }  // namespace gm

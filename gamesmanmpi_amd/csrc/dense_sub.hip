@@ -35,6 +35,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 
 #include <algorithm>
@@ -1268,6 +1269,17 @@ static int dense_sub_verify(Ctx *c, const VerifyDev &v) {
     return GM_OK;
 }
 
+// gm_moves: slot = key in the one table (moves_common.hpp)
+static int dense_sub_moves(Ctx *c, const MovesReq &r) {
+    DenseSub *d = c->dsub;
+    DevBuf<const uint8_t *> tabs;
+    GM_TRY(tabs.alloc(1));
+    const uint8_t *t = d->table;
+    GM_HIP(hipMemcpyAsync(tabs, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));   // t leaves scope
+    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<0>(c, mv, tabs.p, nullptr, 0, d->heaps); });
+}
+
 // a key of the root's region of a SUBTRACT table of `heaps` heaps
 static bool sub_key_held(const Ctx *c, uint64_t k, int heaps) {
     if (heaps < 16 && (k >> (4 * heaps))) return false;
@@ -1382,6 +1394,6 @@ static int dense_sub_import(Ctx *c, const void *keys_, const uint16_t *recs, uin
 
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
                  dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_select, dense_sub_table, dense_sub_free,
-                 dense_sub_verify, dense_sub_poke, dense_sub_import)
+                 dense_sub_verify, dense_sub_poke, dense_sub_import, dense_sub_moves)
 
 }  // namespace gm

@@ -45,6 +45,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
@@ -1503,6 +1504,12 @@ static int dist_box_select(Ctx *c, const SelectDev &s) {
     return GM_OK;
 }
 
+// gm_moves: every code read from its box's holder, as box_launch_query reads it (moves_common.hpp)
+static int dist_box_moves(Ctx *c, const MovesReq &r) {
+    DistBox *d = c->dist_box;
+    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<1>(c, mv, d->d_tables, d->d_owner, 0, 8); });
+}
+
 // gm_verify over every virtual rank's own boxes; each code, a position's own and its children's,
 // is read from its box's holder as box_launch_query reads it (d_owner, d_tables)
 static int dist_box_verify(Ctx *c, const VerifyDev &v) {
@@ -1697,6 +1704,6 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
 
 GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
                  dist_box_query, dist_box_digest, dist_box_histogram, dist_box_select, dist_box_table, dist_box_free,
-                 dist_box_verify, dist_box_poke)
+                 dist_box_verify, dist_box_poke, nullptr, dist_box_moves)
 
 }  // namespace gm

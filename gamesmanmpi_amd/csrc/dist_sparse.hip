@@ -1350,6 +1350,12 @@ static int dist_sparse_verify(Ctx *c, const VerifyDev &v) {
     });
 }
 
+static int dist_sparse_moves(Ctx *c, const MovesReq &r) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        return tiers_moves(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), r);
+    });
+}
+
 static int dist_sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     if (c->wide) {
         K128 k;
@@ -1413,6 +1419,6 @@ static int dist_sparse_import(Ctx *c, const void *keys, const uint16_t *recs, ui
 
 GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
                  dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, dist_sparse_select, nullptr, dist_sparse_free,
-                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import)
+                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import, dist_sparse_moves)
 
 }  // namespace gm

@@ -62,6 +62,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 
 #include <mutex>
@@ -860,6 +861,26 @@ static int dist_sub_verify(Ctx *c, const VerifyDev &v) {
     return GM_OK;
 }
 
+// gm_moves: every code read from the table of its block's owner, as dist_sub_verify reads it
+// (moves_common.hpp)
+static int dist_sub_moves(Ctx *c, const MovesReq &r) {
+    DistSub *d = c->dist_sub;
+    std::vector<uint8_t> own(1ull << (4 * d->high));
+    for (uint64_t H = 0; H < own.size(); H++) own[H] = holder_of(d, H);
+    std::vector<const uint8_t *> tabs;
+    for (auto &R : d->ranks) tabs.push_back(R.table);
+    DevBuf<uint8_t> d_own;
+    DevBuf<const uint8_t *> d_tabs;
+    GM_TRY(d_own.alloc(own.size()));
+    GM_TRY(d_tabs.alloc(tabs.size()));
+    GM_HIP(hipMemcpyAsync(d_own, own.data(), own.size(), hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipMemcpyAsync(d_tabs, tabs.data(), tabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    return moves_run(c, r, [&](const MovesDev &mv) {
+        return byte_moves_launch<0>(c, mv, d_tabs.p, d_own.p, 4 * d->low, d->heaps);
+    });
+}
+
 static int dist_sub_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     DistSub *d = c->dist_sub;
     const uint64_t k = words[0];
@@ -986,6 +1007,6 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
 
 GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
                  dist_sub_query, dist_sub_digest, dist_sub_histogram, dist_sub_select, nullptr, dist_sub_free,
-                 dist_sub_verify, dist_sub_poke)
+                 dist_sub_verify, dist_sub_poke, nullptr, dist_sub_moves)
 
 }  // namespace gm

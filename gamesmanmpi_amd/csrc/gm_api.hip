@@ -3,6 +3,9 @@
 #include "hist_common.hpp"
 #include "verify_common.hpp"
 #include "select_common.hpp"
+#include "moves_common.hpp"
+
+#include <hipcub/hipcub.hpp>
 
 #include <chrono>
 #include <stdlib.h>
@@ -125,6 +128,98 @@ static const Engine *choose_engine(const Ctx *c, bool sharded) {
 
 static bool key_valid(const Ctx *c, uint64_t k) {
     return with_desc(c, [&](const auto &d) { return (int)d.valid(k); }) > 0;
+}
+
+// keys per chunk of gm_moves: GM_MOVES_CHUNK (a development variable, as GM_SPARSE_BATCH) lets a
+// test cross a chunk boundary with a small table
+static uint64_t moves_chunk() {
+    const char *e = getenv("GM_MOVES_CHUNK");
+    const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+    return v ? std::min<uint64_t>(v, 1ull << 30) : MOVES_CHUNK;   // the scan counts its items in an int
+}
+
+// The chunk loop of gm_moves (moves_common.hpp).  Per chunk: keys up, the engine's count pass,
+// the exclusive sum of the counts (one slot past the chunk holds 0, so its sum is the chunk's
+// total), the engine's fill pass into child buffers of exactly that total, heads and children
+// down at the running offset.  The caller's child arrays must stay untouched when they are too
+// small, and the total is known only after every chunk's count pass: a call of more than one
+// chunk that wants children counts all chunks first.
+int moves_run(Ctx *c, const MovesReq &r, const std::function<int(const MovesDev &)> &pass) {
+    *r.n_children = 0;
+    if (!r.n) return GM_OK;
+    const uint64_t chunk = std::min(r.n, moves_chunk());
+    const int W = r.words;
+    bool want = r.child_words && r.cap;
+    DevBuf<unsigned char> dk, dscan;
+    DevBuf<uint64_t> dcount, dfirst, dcw;
+    DevBuf<uint16_t> dcr;
+    DevBuf<gm_moves_t> dh;
+    GM_TRY(dk.alloc(chunk * r.key_bytes));
+    GM_TRY(dcount.alloc(chunk + 1));
+    GM_TRY(dfirst.alloc(chunk + 1));
+    GM_TRY(dh.alloc(chunk));
+    size_t scan_bytes = 0;
+    GM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, dcount.p, dfirst.p, (int)(chunk + 1), c->stream));
+    GM_TRY(dscan.alloc(std::max<size_t>(scan_bytes, 1)));
+    // the count pass and the scan of keys [o, o + m): *ct = the chunk's children
+    auto count_chunk = [&](uint64_t o, uint64_t m, MovesDev *mv, uint64_t *ct) -> int {
+        GM_HIP(hipMemcpyAsync(dk, (const unsigned char *)r.keys + o * r.key_bytes, m * r.key_bytes, hipMemcpyHostToDevice,
+                              c->stream));
+        GM_HIP(hipMemsetAsync(dcount.p + m, 0, 8, c->stream));
+        *mv = MovesDev{dk.p, m, dcount.p, dfirst.p, dh.p, nullptr, nullptr, 0, 0};
+        GM_TRY(pass(*mv));
+        GM_HIP(hipcub::DeviceScan::ExclusiveSum(dscan.p, scan_bytes, dcount.p, dfirst.p, (int)(m + 1), c->stream));
+        GM_HIP(hipMemcpyAsync(ct, dfirst.p + m, 8, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));
+        return GM_OK;
+    };
+    MovesDev mv;
+    uint64_t ct = 0;
+    if (want && r.n > chunk) {
+        uint64_t total = 0;
+        for (uint64_t o = 0; o < r.n; o += chunk) {
+            GM_TRY(count_chunk(o, std::min(chunk, r.n - o), &mv, &ct));
+            total += ct;
+        }
+        want = total <= r.cap;
+    }
+    uint64_t base = 0, have_w = 0, have_r = 0;
+    for (uint64_t o = 0; o < r.n; o += chunk) {
+        const uint64_t m = std::min(chunk, r.n - o);
+        GM_TRY(count_chunk(o, m, &mv, &ct));
+        if (want && base + ct > r.cap) want = false;   // one chunk: nothing has been written yet
+        if (want && ct) {
+            if (have_w < ct) {
+                if (dcw.p) { (void)hipFree(dcw.p); dcw.p = nullptr; }
+                GM_TRY(dcw.alloc(ct * W));
+                have_w = ct;
+            }
+            if (r.child_records && have_r < ct) {
+                if (dcr.p) { (void)hipFree(dcr.p); dcr.p = nullptr; }
+                GM_TRY(dcr.alloc(ct));
+                have_r = ct;
+            }
+            mv.child_words = dcw.p;
+            mv.child_records = r.child_records ? dcr.p : nullptr;
+        }
+        mv.base = base;
+        mv.fill = 1;
+        GM_TRY(pass(mv));
+        GM_HIP(hipMemcpyAsync(r.heads + o, dh.p, m * sizeof(gm_moves_t), hipMemcpyDeviceToHost, c->stream));
+        if (mv.child_words) {
+            GM_HIP(hipMemcpyAsync(r.child_words + base * W, dcw.p, ct * W * 8, hipMemcpyDeviceToHost, c->stream));
+            if (mv.child_records)
+                GM_HIP(hipMemcpyAsync(r.child_records + base, dcr.p, ct * 2, hipMemcpyDeviceToHost, c->stream));
+        }
+        GM_HIP(hipStreamSynchronize(c->stream));
+        base += ct;
+    }
+    *r.n_children = base;
+    if (r.child_words && r.cap && base > r.cap) {
+        set_error("gm_moves: the child arrays hold %llu, need %llu", (unsigned long long)r.cap, (unsigned long long)base);
+        return GM_E_CAP;
+    }
+    return GM_OK;
 }
 
 static void free_engines(Ctx *c) {
@@ -889,6 +984,31 @@ int gm_select(gm_ctx *h, const gm_select_t *what, uint64_t *key_words, uint16_t 
         if (records) records[i] = rr[idx[i]];
     }
     return GM_OK;
+}
+
+int gm_moves(gm_ctx *h, const uint64_t *key_words, uint64_t n, gm_moves_t *heads, uint64_t *child_words,
+             uint16_t *child_records, uint64_t cap, uint64_t *n_children) {
+    if (!h || !n_children) { set_error("gm_moves: ctx or n_children is NULL"); return GM_E_ARG; }
+    if (n && (!key_words || !heads)) { set_error("gm_moves: key_words or heads is NULL"); return GM_E_ARG; }
+    GM_TRY(need_solved(h));
+    Ctx *c = &h->c;
+    GM_TRY(need_whole_table(c, "gm_moves"));
+    if (!c->solved_by->moves) { set_error("gm_moves: this engine's tables do not answer moves"); return GM_E_STATE; }
+    *n_children = 0;
+    if (!n) return GM_OK;
+    GM_HIP(hipSetDevice(c->device));
+    MovesReq r{key_words, 8, 1, n, heads, child_words, child_records, cap, n_children};
+    std::vector<K128> wide_keys;
+    if (c->wide) {
+        wide_keys.resize(n);
+        for (uint64_t i = 0; i < n; i++)
+            if (!DescOthello8::from_words(key_words + (size_t)WIDE_WORDS * i, &wide_keys[i]))
+                wide_keys[i] = K128{0, 0};   // no valid key: record 0xFFFF, no children
+        r.keys = wide_keys.data();
+        r.key_bytes = sizeof(K128);
+        r.words = WIDE_WORDS;
+    }
+    return c->solved_by->moves(c, r);
 }
 
 int gm_poke(gm_ctx *h, const uint64_t *key_words, uint16_t record) {

@@ -64,6 +64,7 @@ struct Graph;
 struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
 struct VerifyDev;   // verify_common.hpp: the device accumulator of gm_verify
 struct SelectDev;   // select_common.hpp: the filter and the device accumulator of gm_select
+struct MovesReq;    // moves_common.hpp: the keys and the output arrays of gm_moves
 struct Engine;
 
 struct Ctx {
@@ -148,7 +149,7 @@ struct Ctx {
 // One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
 // record next to its functions; gm_solve picks one per solve from the context's options
 // (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
-// of the solved table (export, query, digest, histogram, select, verify, dense table, rank stats) goes through it.
+// of the solved table (export, query, digest, histogram, select, verify, moves, dense table, rank stats) goes through it.
 struct Engine {
     int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
     int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
@@ -165,6 +166,9 @@ struct Engine {
     // uint64_t, or K128 on a wide context.  Sets n_positions, tier_counts and the table's share of
     // stats; on failure the caller frees the engine.  null: the engine's tables cannot be imported
     int (*import_)(Ctx *c, const void *keys, const uint16_t *recs, uint64_t n);
+    // gm_moves: every key's record, children (the plugin's gen_moves order), their records and
+    // the mover's choice into the request's arrays (moves_common.hpp)
+    int (*moves)(Ctx *c, const MovesReq &r);
 };
 // A record is host data, defined in the host pass only: the device pass of a translation unit
 // would emit a const record too, with references to the host functions it names.

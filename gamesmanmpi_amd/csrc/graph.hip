@@ -18,6 +18,7 @@
 #include "graph_common.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 
 #include <algorithm>
@@ -287,6 +288,53 @@ static int graph_verify(Ctx *c, const VerifyDev &v) {
     return GM_OK;
 }
 
+// gm_moves over node indices (moves_common.hpp): the children are the CSR's, in its order; a
+// key >= n has no record; a DRAW child of a loopy table ranks between TIE and WIN (moves_rank).
+// The count and the choice are 16-bit in gm_moves_t: a node lists at most 32,767 children.
+__global__ __launch_bounds__(256) void graph_moves_kernel(const uint8_t *__restrict__ prim,
+                                                          const uint64_t *__restrict__ off,
+                                                          const uint32_t *__restrict__ kid,
+                                                          const uint16_t *__restrict__ score, uint64_t n, MovesDev mv) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < mv.m; i += (uint64_t)gridDim.x * 256ull) {
+        const uint64_t k = ((const uint64_t *)mv.keys)[i];
+        if (!mv.fill) {
+            const uint16_t rec = k < n ? graph_record(score[k]) : REC_UNSOLVED;
+            uint32_t cnt = 0;
+            if (rec != REC_UNSOLVED && prim[k] == UNDECIDED) cnt = (uint32_t)min(off[k + 1] - off[k], (uint64_t)0x7FFF);
+            mv.count[i] = cnt;
+            mv.heads[i] = moves_head(0, cnt, -1, rec, 0);
+            continue;
+        }
+        gm_moves_t h = mv.heads[i];
+        const uint64_t first = mv.first[i];
+        h.first = mv.base + first;
+        if (h.count) {
+            MovesBest best;
+            const uint64_t e0 = off[k];
+            for (uint32_t pos = 0; pos < h.count; pos++) {
+                const uint32_t ch = kid[e0 + pos];
+                const uint16_t rec = ch < n ? graph_record(score[ch]) : REC_UNSOLVED;
+                if (mv.child_words) mv.child_words[first + pos] = ch;
+                if (mv.child_records) mv.child_records[first + pos] = rec;
+                best.add(moves_rank(rec), pos);
+            }
+            h.best = (int16_t)best.at;
+            h.n_best = (uint16_t)best.n;
+        }
+        mv.heads[i] = h;
+    }
+}
+
+static int graph_moves(Ctx *c, const MovesReq &r) {
+    Graph *g = c->graph;
+    return moves_run(c, r, [&](const MovesDev &mv) {
+        hipLaunchKernelGGL(graph_moves_kernel, dim3(grid_counted(mv.m)), dim3(256), 0, c->stream, g->prim, g->off, g->kid,
+                           g->score, g->n, mv);
+        GM_HIP(hipGetLastError());
+        return GM_OK;
+    });
+}
+
 static int graph_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     Graph *g = c->graph;
     if (words[0] >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
@@ -309,6 +357,7 @@ void graph_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(graph_engine, GM_ENGINE_GRAPH, nullptr, graph_export,
-                 graph_query, graph_digest, graph_histogram, graph_select, nullptr, graph_free, graph_verify, graph_poke)
+                 graph_query, graph_digest, graph_histogram, graph_select, nullptr, graph_free, graph_verify, graph_poke,
+                 nullptr, graph_moves)
 
 }  // namespace gm

@@ -9,6 +9,7 @@
 #include "gm_internal.hpp"
 #include "hist_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 
 namespace gm {
@@ -199,6 +200,12 @@ __global__ __launch_bounds__(256) void small_verify_kernel(D d, const uint16_t *
     verify_flush(v, t);
 }
 
+// gm_moves from the host records gm_query answers from (moves_common.hpp moves_host)
+static int small_dense_moves(Ctx *c, const MovesReq &r) {
+    SmallDense *s = c->sd;
+    return moves_host(c->ttt, r, [&](uint64_t k) { return k < s->slots ? s->h_rec[k] : REC_UNSOLVED; });
+}
+
 static int small_dense_verify(Ctx *c, const VerifyDev &v) {
     SmallDense *s = c->sd;
     hipLaunchKernelGGL(small_verify_kernel<DescTTT>, dim3(grid_counted(s->slots)), dim3(256), 0, c->stream, c->ttt,
@@ -273,6 +280,6 @@ static int small_dense_import(Ctx *c, const void *keys_, const uint16_t *recs, u
 
 GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
                  small_dense_query, small_dense_digest, small_dense_histogram, small_dense_select, nullptr, small_dense_free,
-                 small_dense_verify, small_dense_poke, small_dense_import)
+                 small_dense_verify, small_dense_poke, small_dense_import, small_dense_moves)
 
 }  // namespace gm

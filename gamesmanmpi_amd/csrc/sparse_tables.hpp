@@ -17,6 +17,7 @@
 #pragma once
 #include "sparse_common.hpp"
 #include "verify_common.hpp"
+#include "moves_common.hpp"
 #include "select_common.hpp"
 
 namespace gm {
@@ -555,6 +556,30 @@ __global__ __launch_bounds__(256) void res_verify_kernel(D d, const typename KT<
     verify_flush(v, tally);
 }
 
+// gm_moves over tier tables (moves_common.hpp).  The G x ntabs matrix of res_verify_kernel; a
+// key's record is query_kernel's answer: valid, its tier one of the tables', its representative
+// found in its owner's table of that tier.
+template <class K>
+struct TierTabs {
+    const typename KT<K>::Res *tabs;
+    int G, ntabs;
+    int64_t t_root;
+    template <class D>
+    __device__ __forceinline__ uint16_t record(const D &d, const K &k) const {
+        if (!d.valid(k)) return REC_UNSOLVED;
+        const int64_t t = d.tier(k) - t_root;
+        if (t < 0 || t >= ntabs) return REC_UNSOLVED;
+        const K cc = d.canon(k);
+        const int s = res_find(tabs[(size_t)owner_rank(cc, (uint32_t)G) * ntabs + t], cc);
+        return s >= 0 ? record_of_score((uint16_t)s) : REC_UNSOLVED;
+    }
+};
+template <class D>
+__global__ __launch_bounds__(256) void res_moves_kernel(D d, TierTabs<key_t<D>> tab, MovesDev mv) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < mv.m; i += (uint64_t)gridDim.x * 256ull)
+        moves_of_key(d, tab, mv, i);
+}
+
 // gm_poke: the score of key's slot overwritten, or (remove) the slot emptied; *found = 1 if held
 template <class K>
 __global__ void res_poke_kernel(typename KT<K>::Res t, K key, uint64_t score, int remove, uint32_t *found) {
@@ -845,6 +870,22 @@ inline int tiers_verify(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>
     GM_HIP(hipGetLastError());
     GM_HIP(hipStreamSynchronize(c->stream));   // tabs leaves scope
     return GM_OK;
+}
+
+// gm_moves over tier tables: group g holds the keys of owner rank g (one group: the one-GPU engine)
+template <class D>
+inline int tiers_moves(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>> &groups, const MovesReq &r) {
+    using K = key_t<D>;
+    DevBuf<typename KT<K>::Res> tabs;
+    int ntabs = 0;
+    GM_TRY(tiers_matrix<K>(c, groups, &tabs, &ntabs));
+    const TierTabs<K> tab{tabs.p, (int)groups.size(), ntabs, groups.empty() ? 0 : groups[0].t_root};
+    return moves_run(c, r, [&](const MovesDev &mv) {
+        // random probes whose workgroups finish unevenly: grid_for's 8,192, as the insert kernels
+        hipLaunchKernelGGL(res_moves_kernel<D>, dim3(grid_for(mv.m)), dim3(256), 0, c->stream, d, tab, mv);
+        GM_HIP(hipGetLastError());
+        return GM_OK;
+    });   // moves_run ends synchronised: tabs may leave scope
 }
 
 // gm_poke in tier tables: the representative's slot in its owner's table of its tier

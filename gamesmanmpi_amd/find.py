@@ -123,11 +123,13 @@ def format_lines(n, rows, spec):
     return lines
 
 
-def report(solver, specs, cap, out, statsdir=None, rank=0, world=1, sharded=False):
+def report(solver, specs, cap, out, statsdir=None, rank=0, world=1, sharded=False, moves=False):
     """--find: per spec, the count and up to `cap` positions ascending by key, written by rank 0
     (and to DIR/stats/find.json with -sd DIR).  Sharded ranks each select among their own keys;
     the counts are summed and the rows merged over the process group, and ``:max`` is resolved
-    from the histogram summed over the ranks."""
+    from the histogram summed over the ranks.  With `moves` every row is followed by the moves
+    of its position, indented two more spaces; the moves of all rows of all specs come from one
+    Solver.annotate call (not for a solve sharded over processes: no rank holds the table)."""
     import json
     import os
     from .solver import split_record
@@ -160,9 +162,17 @@ def report(solver, specs, cap, out, statsdir=None, rank=0, world=1, sharded=Fals
         found.append((spec, n, rows, keys))
     if rank != 0:
         return
+    if moves and not gather:
+        from .moves import format_rows
+        notes = iter(solver.annotate([row[0] for _, _, rows, _ in found for row in rows]))
     for spec, n, rows, _ in found:
-        for ln in format_lines(n, rows, spec):
+        lines = format_lines(n, rows, spec)
+        out.write(lines[0] + "\n")
+        for ln in lines[1:]:
             out.write(ln + "\n")
+            if moves and not gather:
+                for mv in format_rows(next(notes)[0], indent="    "):
+                    out.write(mv + "\n")
     out.flush()
     if statsdir:
         path = os.path.join(statsdir, "stats", "find.json")

@@ -248,6 +248,35 @@ class Context:
         recs = self.query(kids)
         return kids, recs, best_move(recs)[0]
 
+    def moves_batch(self, keys, children=True):
+        """gm_moves: every key's record, children and the mover's choice from one device call.
+        Keys as query() takes them, in any order, repeats allowed.  Returns (heads, child_keys,
+        child_records): heads a structured array (_lib.moves_dtype: first, count, best, record,
+        n_best), child_keys of shape (total,) -- (total, words) for multi-word keys -- in key
+        order, each key's children in the plugin's gen_moves order, child_records their u16
+        records.  children=False: heads only (child_keys and child_records None)."""
+        keys = self.key_array(keys)
+        n = len(keys)
+        heads = np.zeros(n, dtype=_lib.moves_dtype())
+        total = ctypes.c_uint64()
+        kp = keys.ctypes.data if n else None
+        hp = heads.ctypes.data if n else None
+        if not children:
+            _lib.check(self.L.gm_moves(self.h, kp, n, hp, None, None, 0, ctypes.byref(total)))
+            return heads, None, None
+        cap = 12 * n + 64   # a guess; a batch with more children is asked again with its total
+        while True:
+            ck = np.empty((cap, self.words), dtype=np.uint64)
+            cr = np.empty(cap, dtype=np.uint16)
+            rc = self.L.gm_moves(self.h, kp, n, hp, ck.ctypes.data, cr.ctypes.data, cap, ctypes.byref(total))
+            if rc == -8 and total.value > cap:   # GM_E_CAP: heads and the total are set
+                cap = total.value
+                continue
+            _lib.check(rc)
+            break
+        t = total.value
+        return heads, (ck[:t] if self.words > 1 else ck[:t, 0]), cr[:t]
+
     def stats(self):
         s = _lib.Stats()
         _lib.check(self.L.gm_stats(self.h, ctypes.byref(s)))
@@ -440,6 +469,50 @@ class Solver:
                 labels = list(range(len(kids)))
         rows = [(m, self.codec.pos(k)) + split_record(r) for m, k, r in zip(labels, kids, recs)]
         return rows, (rows[best] if best is not None else None)
+
+    def annotate(self, positions):
+        """moves() for many positions at once: a list with, per position, what moves(pos)
+        returns, from one gm_moves call (Context.moves_batch).  A graph context is looked up by
+        position, as moves() does -- its nodes are orbit representatives under symmetry
+        generators, and its CSR lists each distinct child once where gen_moves may not -- with
+        one batched query for all the children."""
+        positions = list(positions)
+        if self.codec.game_id == _lib.GAME_GRAPH:
+            labels = [list(self.module.gen_moves(p)) if self.module.primitive(p) == UNDECIDED else None
+                      for p in positions]
+            kids = [[self.codec.key(self.module.do_move(p, m)) for m in ms] if ms is not None else []
+                    for p, ms in zip(positions, labels)]
+            flat = [k for ks in kids for k in ks]
+            recs = self.ctx.query(flat) if flat else np.zeros(0, dtype=np.uint16)
+            out, at = [], 0
+            for ms, ks in zip(labels, kids):
+                if ms is None:
+                    out.append(([], None))
+                    continue
+                rs = recs[at:at + len(ks)]
+                at += len(ks)
+                best = best_move(rs)[0]
+                rows = [(m, self.codec.pos(k)) + split_record(r) for m, k, r in zip(ms, ks, rs)]
+                out.append((rows, rows[best] if best is not None else None))
+            return out
+        heads, ck, cr = self.ctx.moves_batch([self.codec.key(p) for p in positions])
+        out = []
+        for pos, h in zip(positions, heads):
+            if self.module.primitive(pos) != UNDECIDED:
+                out.append(([], None))
+                continue
+            if int(h["record"]) == _lib.REC_UNSOLVED:   # not in the table: gm_moves lists nothing, moves() expands
+                out.append(self.moves(pos))
+                continue
+            first, count = int(h["first"]), int(h["count"])
+            kids = ck[first:first + count]
+            kids = [int(k) for k in kids] if self.ctx.words == 1 else [_lib.words_to_int(k) for k in kids]
+            labels = list(self.module.gen_moves(pos))
+            if len(labels) != len(kids):   # a plugin that lists a move twice: number the children
+                labels = list(range(len(kids)))
+            rows = [(m, self.codec.pos(k)) + split_record(r) for m, k, r in zip(labels, kids, cr[first:first + count])]
+            out.append((rows, rows[int(h["best"])] if count else None))
+        return out
 
     def find(self, spec_or_values, rem=None, cap=16, with_keys=False):
         """The positions with a given value and remoteness, selected on the device (gm_select).

@@ -463,6 +463,52 @@ typedef struct {
 int gm_select(gm_ctx *ctx, const gm_select_t *what, uint64_t *key_words, uint16_t *records, uint64_t cap,
               uint64_t *n);
 
+/* One key's answer from gm_moves. */
+typedef struct {
+    uint64_t first;    /* index of this key's first child in child_words / child_records */
+    uint16_t count;    /* its children; 0: primitive, or no record (record == 0xFFFF) */
+    int16_t  best;     /* index among its children of the move the solver plays; -1 when count == 0 */
+    uint16_t record;   /* the key's own record, exactly what gm_query / gm_query_key returns */
+    uint16_t n_best;   /* children whose rank equals the best child's: the optimal moves */
+} gm_moves_t;          /* 16 bytes */
+
+/* What the mover can do at each of n positions, what every move is worth and which one perfect
+ * play chooses, computed on the device in one call: gm_verify's edge pass (parent -> children ->
+ * records) over the caller's keys, with the children, their records and the choice as output.
+ * Keys: n keys of gm_key_words() words each, in any order, repeats allowed; one call serves
+ * one-word and multi-word contexts.
+ * Children: a key's children are the plugin's own moves in gen_moves order, exactly the keys
+ * gm_expand_host / gm_expand_host_key returns for it: the unreduced descriptor under
+ * GM_OPT_SYMMETRY (a child need not be canonical), Othello's squares x outer, y inner at 4x4 and
+ * 8x8, the pass child (key + 1 at 4x4).  On a GM_GAME_GRAPH context keys are node indices and the
+ * children are the CSR's child_idx entries in order (at most 32,767 of a node are listed).  A
+ * primitive key has count 0.
+ * Child records: what gm_query would return for the child key -- through the symmetry
+ * representative, across all virtual ranks, after gm_poke / gm_import following the table --
+ * and 0xFFFF when the child has no record.
+ * best is the first child of maximal rank, n_best the number of children of that rank.  The
+ * rank orders LOSS (shortest) > TIE (shortest) > DRAW > WIN (longest) > 0xFFFF: the argmin /
+ * argmax of GameState.compare_gamestates (src/game_state.py:105-125, src/utils.py:90-105), with
+ * the DRAW of a loopy graph solve between TIE and WIN.
+ * A key that is invalid, outside the root's region or unreached has record 0xFFFF, count 0,
+ * best -1 and lists no children; nothing about it is an error.
+ * first[i] is the sum of count[j] over j < i: the child arrays are in key order, gap-free and
+ * the same on every run; *n_children is the total.
+ * heads (n entries) is always filled.  child_words == NULL or cap == 0: heads and the total
+ * only.  cap < *n_children: GM_E_CAP, with heads and *n_children set and the child arrays
+ * untouched.  child_records may be NULL.  n == 0: GM_OK with *n_children = 0.
+ * GM_E_ARG (checked first): n_children is NULL, or n > 0 with key_words or heads NULL.
+ * GM_E_STATE before a solve and after a failed solve or import; GM_E_STATE on a rank of a
+ * multi-process solve, which does not hold the tables of its children's owners (as gm_verify;
+ * virtual ranks are answered as one table).
+ * Keys are uploaded and answers downloaded in chunks (GM_MOVES_CHUNK keys, a development
+ * variable; default 2^20), so n is not bounded by a device allocation.
+ * Replaces, for a batch, reopening the `resolved` shelves and calling the plugin's gen_moves /
+ * do_move per position (src/cache_dict.py:38-79, src/game_state.py:33-41), the reference's only
+ * route from a solved table to its moves. */
+int gm_moves(gm_ctx *ctx, const uint64_t *key_words, uint64_t n, gm_moves_t *heads, uint64_t *child_words,
+             uint16_t *child_records, uint64_t cap, uint64_t *n_children);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

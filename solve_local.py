@@ -2,7 +2,7 @@
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
     python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
-                          [--loopy] [--load DIR] [--find SPEC ...] [--find-cap N] [--line]
+                          [--loopy] [--load DIR] [--find SPEC ...] [--find-cap N] [--line] [--moves]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -17,7 +17,9 @@ offending positions; the exit status is non-zero when the table is inconsistent)
 ``--find SPEC`` (repeatable) prints ``Found N positions: SPEC`` and up to ``--find-cap`` (16)
 positions with that value and remoteness, selected on the device (gm_select,
 gamesmanmpi_amd/find.py; a bad spec exits 2 before the solve), and ``--line`` the principal
-variation from the root, one row per ply.
+variation from the root, one row per ply.  ``--moves`` prints ``Moves:`` and the root's moves, each
+with its child position and value and a trailing `` *`` on every optimal one; with ``--find`` every
+position found is followed by its own moves instead (gm_moves, gamesmanmpi_amd/moves.py).
 ``--loopy`` solves a game in which positions can repeat (explicit graph, GM_OPT_LOOPY): "Draw"
 is then a real answer, ``--remoteness`` prints ``DRAW`` alone for it and ``--analysis`` adds a
 line ``Draw  N`` under its table.  ``--load DIR`` takes the place of the solve: the
@@ -53,6 +55,8 @@ def build_parser():
                    help="name the positions with a value and remoteness: VALUE[,VALUE...][:R | :LO-HI | :max]")
     p.add_argument("--find-cap", type=int, default=16, metavar="N")
     p.add_argument("--line", action="store_true", help="print the principal variation from the root")
+    p.add_argument("--moves", action="store_true",
+                   help="print the root's moves with their values, or with --find the moves of every position found")
     p.add_argument("--loopy", action="store_true")
     p.add_argument("--load", metavar="DIR",
                    help="in place of the solve, load the table.npz files a solver_launcher.py -sd DIR run wrote")
@@ -102,13 +106,15 @@ def main(argv=None):
             print("Draw  %d" % s.draw_count())
     if specs:
         from gamesmanmpi_amd import find
-        find.report(s, specs, max(0, args.find_cap), sys.stdout)
+        find.report(s, specs, max(0, args.find_cap), sys.stdout, moves=args.moves)
     if args.line:
         solver_launcher.write_line(s, sys.stdout)
     status = 0
     if args.verify:
         from gamesmanmpi_amd import verify
         status = 0 if verify.report(s, sys.stdout) else 1
+    if args.moves and not specs:
+        solver_launcher.write_moves(s, sys.stdout)
     s.close()
     return status
 

@@ -49,6 +49,12 @@ Differences, on purpose:
 * ``--line`` prints ``Line:`` and the principal variation from the root, one row per ply
   (``  K. <move> -> <position>: TIE in 8``); like ``--verify`` it needs the whole table in one
   process and is refused (exit status 2) when the solve is sharded over processes;
+* ``--moves`` prints ``Moves:`` and one line per move of the root (``  <move> -> <child position>:
+  <VALUE> in <R>``, a trailing `` *`` on every optimal move) after everything above; together
+  with ``--find`` every position found is followed by its own moves instead, indented two more
+  spaces, all of them valued by one device call (gm_moves, gamesmanmpi_amd/moves.py).  A solve
+  sharded over processes goes ahead without the moves and says so in one line on stderr: no
+  rank holds the whole table (``--load DIR`` of its ``-sd`` output does);
 * ``--loopy`` is for games in which a position can repeat: the plugin is enumerated on the
   host and solved as an explicit graph with cycles allowed (GM_OPT_LOOPY, one process); a
   position neither side can decide is a draw, the root line of a drawn root is ``DRAW``
@@ -104,6 +110,8 @@ def build_parser():
                         "VALUE[,VALUE...][:R | :LO-HI | :max] (repeatable)")
     p.add_argument("--find-cap", type=int, default=16, metavar="N", help="positions printed per --find (default 16)")
     p.add_argument("--line", action="store_true", help="after the root line, print the principal variation from the root")
+    p.add_argument("--moves", action="store_true",
+                   help="print the root's moves with their values, or with --find the moves of every position found")
     p.add_argument("--loopy", action="store_true",
                    help="solve a game with cycles: explicit graph, undecidable positions are DRAW")
     p.add_argument("--load", metavar="DIR",
@@ -225,6 +233,12 @@ def run(args, out=sys.stdout):
                 print("--line needs the whole table in one process: this solve is sharded over %d processes.  Run it "
                       "on one process (virtual ranks included)." % world, file=sys.stderr)
             return 2
+        if plan == "sharded" and getattr(args, "moves", False):
+            # no refusal: the solve and everything else asked for go ahead without the moves
+            if rank == 0:
+                print("--moves needs the whole table in one process: this solve is sharded over %d processes; solve "
+                      "with -sd DIR, then ask for the moves of the stored table (--load DIR)" % world, file=sys.stderr)
+            args.moves = False
         if plan == "sharded" and getattr(args, "load", None):
             if rank == 0:
                 print("--load builds the whole table in one process: run it on one process, or with more ranks than "
@@ -297,13 +311,15 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     if find_specs(args):
         from gamesmanmpi_amd import find
         find.report(solver, find_specs(args), max(0, args.find_cap), out, args.statsdir, rank, world,
-                    sharded=plan == "sharded")
+                    sharded=plan == "sharded", moves=getattr(args, "moves", False))
     if getattr(args, "line", False) and rank == 0:
         write_line(solver, out)
     status = 0
     if getattr(args, "verify", False) and rank == 0:
         from gamesmanmpi_amd import verify
         status = 0 if verify.report(solver, out, args.statsdir) else 1
+    if getattr(args, "moves", False) and not find_specs(args) and rank == 0:
+        write_moves(solver, out)
     if args.stats:
         st = solver.ctx.stats()
         st["rank"] = rank
@@ -332,6 +348,16 @@ def write_line(solver, out):
     for ply, (move, pos, value, remoteness) in enumerate(solver.line()):
         step = "" if move is None else "%r -> " % (move,)
         out.write("  %d. %s%r: %s\n" % (ply, step, pos, _record_text(value, remoteness)))
+    out.flush()
+
+
+def write_moves(solver, out):
+    """--moves without --find: the root's moves, each with its child position and value, the
+    optimal ones starred (gm_moves through Solver.annotate)."""
+    from gamesmanmpi_amd import moves
+    rows, _ = solver.annotate([solver.root])[0]
+    for ln in moves.format_block(rows):
+        out.write(ln + "\n")
     out.flush()
 
 
