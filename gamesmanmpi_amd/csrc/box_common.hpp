@@ -112,4 +112,32 @@ GM_HD uint32_t bx_swap_key(uint32_t code, uint32_t k) {
     return k ^ (t << (4 * q)) ^ (t << (4 * p));
 }
 
+
+// Mirror of heaps 6 and 7 (the one-GPU box engine, GM_OPT_SYMMETRY).  swap67(C) is box C with
+// the coordinate fields c6 (bits 14-16) and c7 (bits 17-19) exchanged; heaps 6 and 7 are bits 2
+// and 3 of B, so row m of swap67(C) is row m of C with bytes B and swap(B) exchanged: dwords 1
+// and 2 of the 16-byte row exchanged, the row's address inside the box unchanged.  Of a pair
+// {C, swap67(C)} that lies in the root's region whole, the box with c6 > c7 is computed and
+// carries the mirror flag (it also stores its twin); the box with c6 < c7 is mirrored-to and
+// never computed.  Every other region box (c6 == c7, or the twin outside the region) is
+// computed and stored once.
+constexpr uint32_t BX_MIRROR_FLAG = 0x80000000u;   // bit 31 of a compute-list entry (box ids have 20 bits)
+constexpr uint32_t BX_BOX_MASK = 0x000FFFFFu;
+GM_HD uint32_t bx_swap67(uint32_t b) {
+    const uint32_t t = ((b >> 14) ^ (b >> 17)) & 7u;
+    return b ^ (t << 14) ^ (t << 17);
+}
+GM_HD bool box_in_region(uint32_t box, uint32_t root_box) {
+    bool in = true;
+    for (int i = 0; i < 8; i++) in = in && box_coord(box, i) <= box_coord(root_box, i);
+    return in;
+}
+// a region box of the root whose top box is root_box: 0 = computed, stored once; 1 = computed,
+// stored to itself and to swap67(box) (the mirror flag); 2 = mirrored-to (not computed)
+GM_HD int bx_mirror_class(uint32_t box, uint32_t root_box) {
+    const int c6 = box_coord(box, 6), c7 = box_coord(box, 7);
+    if (c6 == c7 || !box_in_region(bx_swap67(box), root_box)) return 0;
+    return c6 > c7 ? 1 : 2;
+}
+
 }  // namespace gm

@@ -38,7 +38,10 @@
 //          zero slot where there is none), (a1, a2) from this lane's own last 1/2/4/8
 //          codes (masked at their digit boundaries) and (a3) from its codes 16 and 32
 //          steps ago (zero before its start); 73 steps, no barrier;
-//   store  16-B rows of both boxes (write-through).
+//   store  16-B rows of both boxes (write-through); the one-GPU tier launches (GM_OPT_SYMMETRY
+//          1) compute only one box of each pair that differs by the exchange of heaps 6 and 7
+//          and store its rows a second time, dwords 1 and 2 exchanged, to the other
+//          (box_common.hpp): 589,824 of the 2^20 boxes computed, all stored.
 // The max of up to 13 inputs uses v_pk_maximum3_f16: a code 0..255 in the low byte of
 // an f16 is a subnormal, ordered like the integer (the kernel keeps f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3).
@@ -67,6 +70,9 @@ typedef uint16_t bx_u16x2 __attribute__((ext_vector_type(2)));
 #endif
 #ifndef GM_BOX_TIER_STORE_CPOL
 #define GM_BOX_TIER_STORE_CPOL GM_BOX_STORE_CPOL   // the tier launches' own (the dataflow kernels keep sc1)
+#endif
+#ifndef GM_BOX_MIRROR_STORE_CPOL
+#define GM_BOX_MIRROR_STORE_CPOL GM_BOX_TIER_STORE_CPOL   // the mirrored box's rows (2 = nt)
 #endif
 #ifndef GM_BOX_WAVES
 #define GM_BOX_WAVES 2         // waves per SIMD the register budget must allow
@@ -186,6 +192,9 @@ struct BxGroup {
     bool valid[2];
 };
 
+// (One-GPU tier launches: the list is a compute list, box_common.hpp, and box[k] keeps the
+// entry's BX_MIRROR_FLAG in bit 31.  Every use of box[k] before bx_store reads coordinate
+// fields or forms the 32-bit offset box << 12, which drop the bit; bx_store masks it.)
 template <bool SHARD, bool FILL = true>
 __device__ __forceinline__ BxGroup bx_group(const uint32_t *__restrict__ boxes, const uint32_t *__restrict__ fills,
                                             const uint32_t *__restrict__ srcs, const uint32_t *__restrict__ dsts,
@@ -598,15 +607,28 @@ __device__ __forceinline__ void bx_walk(uint32_t *s, uint32_t ln, const BxLaneC 
 // so the receiver needs no unpack.
 // (NI rows per lane from row set i0: the one-wave kernel stores all four, a wave of the
 // four-wave kernel its own.)
-template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI = 4>
+// MIRROR (one GPU, box_common.hpp): a box with the mirror flag is also stored, from the same
+// registers with dwords 1 and 2 of each row exchanged, to the same rows of swap67(box), which no
+// workgroup computes; a box without the flag gets a descriptor of size 0, which drops the stores.
+template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI = 4, bool MIRROR = false>
 __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *p0, uint8_t *p1, uint8_t *p2,
                                          const BxGroup &G, const uint32_t *s, uint32_t lane, uint32_t i0 = 0) {
     constexpr bool SHARD = SHARD_ && !(GM_BOX_EXP & 32);
-    __amdgpu_buffer_rsrc_t w[2];
+    static_assert(!(MIRROR && SHARD_), "the mirrored store is the one-GPU tier launches'");
+    __amdgpu_buffer_rsrc_t w[2], wx[2];
 #pragma unroll
-    for (int k = 0; k < 2; k++)
-        w[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)G.box[k] << 12), 0,
+    for (int k = 0; k < 2; k++) {
+        // (MIRROR: box[k] is a compute-list entry, its flag in bit 31, masked here where it
+        // becomes an address)
+        const uint32_t box = MIRROR ? G.box[k] & BX_BOX_MASK : G.box[k];
+        w[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)box << 12), 0,
                                                  (G.valid[k] && !(GM_BOX_EXP & 4)) ? 4096u : 0u, 0x00020000);
+        if constexpr (MIRROR) {
+            const bool mir = G.valid[k] && (G.box[k] & BX_MIRROR_FLAG);
+            wx[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)bx_swap67(box) << 12), 0,
+                                                      (mir && !(GM_BOX_EXP & 4)) ? 4096u : 0u, 0x00020000);
+        }
+    }
     uint32_t dst[2][3] = {{0, 0, 0}, {0, 0, 0}};
     __amdgpu_buffer_rsrc_t wm;
     if constexpr (SHARD) {
@@ -630,6 +652,12 @@ __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *
         }
         __builtin_amdgcn_raw_buffer_store_b128(o[0], w[0], 16u * m, 0, CP);
         __builtin_amdgcn_raw_buffer_store_b128(o[1], w[1], 16u * m, 0, CP);
+        if constexpr (MIRROR) {
+#pragma unroll
+            for (int k = 0; k < 2; k++)
+                __builtin_amdgcn_raw_buffer_store_b128(bx_u32x4{o[k][0], o[k][2], o[k][1], o[k][3]}, wx[k], 16u * m, 0,
+                                                       GM_BOX_MIRROR_STORE_CPOL);
+        }
         if constexpr (SHARD && DIRECT) {
 #pragma unroll
             for (int k = 0; k < 2; k++)
@@ -684,7 +712,9 @@ __device__ unsigned long long bx_trace_acc[8];
 // per box saying where each child box is read from.
 // FILL (split solve): some box of the launch reads a child through a transposition; a launch
 // without (every tier of rank 0, most of the others' first tiers) reads its children as at N = 1.
-template <bool SHARD, bool DIRECT = false, bool FILL = true>
+// MIRROR (one GPU): `boxes` is the tier's compute list (box_common.hpp), and a box with the mirror
+// flag is stored twice (bx_store).
+template <bool SHARD, bool DIRECT = false, bool FILL = true, bool MIRROR = !SHARD>
 __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_tier_kernel(uint8_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ boxes,
                                                                      const uint32_t *__restrict__ fills,
@@ -742,7 +772,7 @@ __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_tier_kernel(uint8_t *__r
 #if GM_BOX_TRACE
         BX_STAMP(tt[3]);
 #endif
-        bx_store<SHARD, DIRECT, GM_BOX_TIER_STORE_CPOL>(table, msg, p0, p1, p2, G, s, ln);
+        bx_store<SHARD, DIRECT, GM_BOX_TIER_STORE_CPOL, 4, MIRROR>(table, msg, p0, p1, p2, G, s, ln);
         BX_LDS_ORDER();
 #if GM_BOX_TRACE
         BX_STAMP(tt[4]);
@@ -1415,6 +1445,11 @@ struct DenseBox {
     uint32_t *d_boxes = nullptr;
     std::vector<uint32_t> tier_off;
     std::vector<uint32_t> boxes;      // host copy (digest list = every box of the region)
+    // the tier launches' compute list (box_common.hpp): the full list without the mirrored-to
+    // boxes, same order, entries box | BX_MIRROR_FLAG; the full list itself with the mirror off
+    bool mirror = false;              // GM_OPT_SYMMETRY when the lists were built
+    uint32_t *d_cboxes = nullptr;
+    std::vector<uint32_t> ctier_off;
     hipGraphExec_t graph = nullptr;
     hipStream_t graph_stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -1510,6 +1545,23 @@ static void box_region_tiers(uint32_t root_hi, std::vector<uint32_t> &boxes, std
     }
 }
 
+// The compute list of a full list (box_common.hpp bx_mirror_class): the mirrored-to boxes
+// dropped, the order (Hilbert inside a tier) kept, so the kernel's 8 XCD runs are runs of the
+// same walk; mirror off: the full list, no flags.
+void box_compute_list(uint32_t root_hi, bool mirror, const std::vector<uint32_t> &boxes,
+                      const std::vector<uint32_t> &tier_off, std::vector<uint32_t> &cboxes,
+                      std::vector<uint32_t> &ctier_off) {
+    cboxes.clear();
+    ctier_off.assign(1, 0);
+    for (size_t t = 0; t + 1 < tier_off.size(); t++) {
+        for (uint32_t i = tier_off[t]; i < tier_off[t + 1]; i++) {
+            const int cls = mirror ? bx_mirror_class(boxes[i], root_hi) : 0;
+            if (cls != 2) cboxes.push_back(boxes[i] | (cls == 1 ? BX_MIRROR_FLAG : 0u));
+        }
+        ctier_off.push_back((uint32_t)cboxes.size());
+    }
+}
+
 static void dense_box_free(Ctx *c);
 
 // A half-built context is never kept: every failure path frees it.
@@ -1526,6 +1578,13 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     box_region_tiers(d->root_hi, d->boxes, d->tier_off);
     GM_HIP(hipMalloc(&d->d_boxes, std::max<size_t>(1, d->boxes.size()) * 4));
     GM_HIP(hipMemcpy(d->d_boxes, d->boxes.data(), d->boxes.size() * 4, hipMemcpyHostToDevice));
+    d->mirror = c->symmetry != 0;
+    {
+        std::vector<uint32_t> cb;
+        box_compute_list(d->root_hi, d->mirror, d->boxes, d->tier_off, cb, d->ctier_off);
+        GM_HIP(hipMalloc(&d->d_cboxes, std::max<size_t>(1, cb.size()) * 4));
+        GM_HIP(hipMemcpy(d->d_cboxes, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
+    }
     d->flow = box_flow_wanted(c);
     if (d->flow) {
         const size_t words = 64 + (1u << 20);
@@ -1586,19 +1645,23 @@ static int box_launch_tiers(Ctx *c, DenseBox *d) {
         const uint32_t nb = d->tier_off[t + 1] - d->tier_off[t];
         if (!nb) continue;
         const uint32_t ng = (nb + 1) / 2;
-        if (ng <= box_thin_groups()) {   // a thin box-tier: the four-wave kernel, one group per workgroup
+        // a thin box-tier: the four-wave kernel, one group per workgroup, over the tier's full list
+        // (it has no mirrored store and computes every box; the table is whole after every launch)
+        if (ng <= box_thin_groups()) {
             hipLaunchKernelGGL(box_tier4_kernel<false>, dim3(ng), dim3(256), 0, c->stream, d->table,
                                d->d_boxes + d->tier_off[t], (const uint32_t *)nullptr, (const uint32_t *)nullptr,
                                (const uint32_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr,
                                (uint8_t *)nullptr, nb);
             continue;
         }
-        // at least 8 workgroups (one per XCD run), at most the resident capacity
-        const uint32_t grid = std::max<uint32_t>(8u, std::min<uint32_t>(ng, (uint32_t)d->grid_cap));
+        // the tier's compute list (never empty where the full list is not: a mirrored-to box's twin
+        // is in its tier); at least 8 workgroups (one per XCD run), at most the resident capacity
+        const uint32_t cnb = d->ctier_off[t + 1] - d->ctier_off[t], cng = (cnb + 1) / 2;
+        const uint32_t grid = std::max<uint32_t>(8u, std::min<uint32_t>(cng, (uint32_t)d->grid_cap));
         hipLaunchKernelGGL(box_tier_kernel<false>, dim3(grid), dim3(64), 0, c->stream, d->table,
-                           d->d_boxes + d->tier_off[t], (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                           d->d_cboxes + d->ctier_off[t], (const uint32_t *)nullptr, (const uint32_t *)nullptr,
                            (const uint32_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr,
-                           (uint8_t *)nullptr, nb);
+                           (uint8_t *)nullptr, cnb);
     }
     GM_HIP(hipGetLastError());
     return GM_OK;
@@ -1626,7 +1689,8 @@ void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc) {
 static int dense_box_solve(Ctx *c, uint64_t root) {
     DenseBox *d = c->dbox;
     const uint32_t rh = box_index_of_key((uint32_t)root) >> 12;
-    if (!d || (c->adopted_dense && d->table != c->adopted_dense) || d->root_hi != rh || d->flow != box_flow_wanted(c)) {
+    if (!d || (c->adopted_dense && d->table != c->adopted_dense) || d->root_hi != rh || d->flow != box_flow_wanted(c) ||
+        d->mirror != (c->symmetry != 0)) {   // (the lists and the captured graph are the option's)
         dense_box_free(c);
         d = c->dbox = new DenseBox();
         const int rc = box_prepare(c, d, root);
@@ -1839,7 +1903,7 @@ static void dense_box_free(Ctx *c) {
     for (auto e : d->ev)
         if (e) (void)hipEventDestroy(e);
     if (d->owned && d->table) (void)hipFree(d->table);
-    for (void *q : {(void *)d->d_boxes, (void *)d->d_groups, (void *)d->d_acc, (void *)d->d_flow, (void *)d->d_tables})
+    for (void *q : {(void *)d->d_boxes, (void *)d->d_cboxes, (void *)d->d_groups, (void *)d->d_acc, (void *)d->d_flow, (void *)d->d_tables})
         if (q) (void)hipFree(q);
     if (d->h_res) (void)hipHostFree(d->h_res);
     delete d;

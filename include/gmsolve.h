@@ -118,7 +118,13 @@ enum {
     GM_OPT_SYMMETRY = 14,   /* sparse engines, symmetry reduction (the reference's unused
                                hook othello_bit_new.py:224-235): 1 (default) = TOOT stores one position
                                per left-right mirror pair when the root is its own mirror image; every
-                               count, export, query and digest still covers both positions.  0 = off */
+                               count, export, query and digest still covers both positions.  0 = off.
+                               Box engine (SUBTRACT, 8 heaps, one GPU, tier launches): 1 (default) = of
+                               two boxes that differ by the exchange of heaps 6 and 7 one is computed
+                               and both are stored (the other's rows are the same rows with dwords 1
+                               and 2 exchanged); every position is still stored, so n_stored stays
+                               n_positions and gm_verify checks them all.  0 = every box computed.
+                               Changing it between solves rebuilds the box lists and the graph */
     GM_OPT_BOX_FLOW = 15,   /* box engine (SUBTRACT, 8 heaps), one GPU: -1 (default) / 0 = one launch per
                                box-tier; 1 = one dataflow launch (box_flow_kernel: a box group starts
                                when its child boxes are stored; its grid is the kernel's resident

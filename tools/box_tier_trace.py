@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Per-box-tier times of the one-GPU 2^32 solve from a rocprofv3 kernel trace.
 
-    python tools/box_tier_trace.py <trace dir> [--json out.json]
+    python tools/box_tier_trace.py <trace dir> [--json out.json] [--mirror] [--last N]
+
+--mirror: the groups of the compute list (GM_OPT_SYMMETRY 1: of the boxes that differ by the
+exchange of heaps 6 and 7 only the one with c6 >= c7 is computed); --last N: the last N solves
+of the trace only (the bench's timed solves, without its warm-up).
 
 The trace is of `bench.py` (one GPU, box engine): every solve is 41 launches of
 box_tier_kernel<false>, box-tier 0 first.  Per box-tier: its groups (two boxes each: the boxes
@@ -19,9 +23,11 @@ import json
 import numpy as np
 
 
-def tier_groups():
+def tier_groups(mirror=False):
     b = np.arange(1 << 20)
     t = sum((b >> (2 * i)) & 3 for i in range(4)) + sum((b >> (8 + 3 * j)) & 7 for j in range(4))
+    if mirror:
+        t = t[((b >> 14) & 7) >= ((b >> 17) & 7)]
     n = np.bincount(t, minlength=41)
     return (n + 1) // 2
 
@@ -31,6 +37,8 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--json", default=None)
     ap.add_argument("--round", type=int, default=2048, help="groups per resident round")
+    ap.add_argument("--mirror", action="store_true", help="groups of the heap-6/7 mirror's compute list")
+    ap.add_argument("--last", type=int, default=0, help="use only the last N solves (0: all)")
     a = ap.parse_args()
     rows = []
     for f in glob.glob(a.trace + "/**/*kernel_trace.csv", recursive=True):
@@ -41,11 +49,13 @@ def main():
     n = len(rows) // 41
     if n == 0:
         raise SystemExit("no complete solve in the trace")
+    if a.last:
+        n = min(n, a.last)
     rows = rows[-41 * n:]
     dur = np.array([(e - s) / 1e3 for s, e in rows]).reshape(n, 41)        # us
     span = np.array([(rows[41 * i + 40][1] - rows[41 * i][0]) / 1e3 for i in range(n)])
     med = np.median(dur, axis=0)
-    g = tier_groups()
+    g = tier_groups(a.mirror)
     thick = g >= 2 * a.round
     rate = g[thick].sum() / med[thick].sum()                                # groups per us
     ideal = g / rate

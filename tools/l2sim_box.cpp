@@ -7,7 +7,12 @@
 // Box layout: the hi bits of every dimension above the lo bits, so a halo slab of a
 // side-4 dimension is a set of whole 256-B chunks; the model counts 256-B chunks.
 //
-//   g++ -O2 -o /tmp/l2sim_box tools/l2sim_box.cpp && /tmp/l2sim_box 44442222 [K] [order]
+//   g++ -O2 -o /tmp/l2sim_box tools/l2sim_box.cpp && /tmp/l2sim_box 44442222 [K] [order] [L2 bytes] [mirror]
+//
+// mirror = 1 (csrc/box_common.hpp, the one-GPU tier launches with GM_OPT_SYMMETRY 1): of each
+// pair of boxes that differ by the exchange of dimensions 6 and 7, only the box with c6 >= c7
+// is computed -- only its child reads are replayed, in the tier's order without the others --
+// and a box with c6 > c7 also writes its twin.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -64,6 +69,7 @@ int main(int argc, char **argv) {
     const int K = argc > 2 ? atoi(argv[2]) : 1;
     const int order = argc > 3 ? atoi(argv[3]) : 0;
     const size_t l2_bytes = argc > 4 ? atoll(argv[4]) : (4u << 20);
+    const int mirror = argc > 5 ? atoi(argv[5]) : 0;
     int s[8], nb[8], lb[8];
     int box_pos = 1;
     for (int i = 0; i < 8; i++) {
@@ -123,10 +129,14 @@ int main(int argc, char **argv) {
     };
     std::vector<LRU> l2(8, LRU(l2_bytes / chunk));
     LRU mall((256u << 20) / chunk);
-    uint64_t l2m = 0, mm = 0, raw = 0, peak_t = 0;
+    uint64_t l2m = 0, mm = 0, raw = 0, peak_t = 0, ncomp = 0;
     for (auto &t : tiers) {
         peak_t = std::max<uint64_t>(peak_t, t.size());
         std::stable_sort(t.begin(), t.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+        if (mirror)   // the compute list: the mirrored-to boxes dropped, the order kept
+            t.erase(std::remove_if(t.begin(), t.end(), [&](uint32_t b) { int c[8]; coords(b, c); return c[6] < c[7]; }),
+                    t.end());
+        ncomp += t.size();
         const uint32_t ng = (t.size() + K - 1) / K;
         std::vector<std::vector<uint32_t>> per(8);
         const uint32_t q = ng >> 3, r = ng & 7;
@@ -167,14 +177,21 @@ int main(int argc, char **argv) {
                         const uint64_t line = (uint64_t)t[idx] * nchunks + qd;
                         mall.touch(line);
                     }
+                    int c[8];
+                    coords(t[idx], c);
+                    if (mirror && c[6] > c[7]) {   // the twin's rows, written by the same group
+                        std::swap(c[6], c[7]);
+                        const uint64_t tw = index(c);
+                        for (int qd = 0; qd < nchunks; qd++) mall.touch(tw * nchunks + qd);
+                    }
                 }
             }
     }
     const double pos = 4294967296.0;
-    printf("sides %s K=%d order=%d L2=%zu KiB: box %d pos, %llu boxes, %d box-tiers (peak %llu boxes), "
-           "in-box sub-tiers %d | halo reads %.2f B/pos, L2-miss %.2f B/pos, MALL-miss %.2f B/pos\n",
-           sides_s, K, order, l2_bytes >> 10, box_pos, (unsigned long long)nbox, maxt + 1,
-           (unsigned long long)peak_t, [&] { int st = 1; for (int i = 0; i < 8; i++) st += s[i] - 1; return st; }(),
+    printf("sides %s K=%d order=%d L2=%zu KiB mirror=%d: box %d pos, %llu boxes (%llu computed), %d box-tiers (peak %llu "
+           "boxes), in-box sub-tiers %d | halo reads %.2f B/pos, L2-miss %.2f B/pos, MALL-miss %.2f B/pos\n",
+           sides_s, K, order, l2_bytes >> 10, mirror, box_pos, (unsigned long long)nbox, (unsigned long long)ncomp,
+           maxt + 1, (unsigned long long)peak_t, [&] { int st = 1; for (int i = 0; i < 8; i++) st += s[i] - 1; return st; }(),
            raw * (double)chunk / pos, l2m * (double)chunk / pos, mm * (double)chunk / pos);
     return 0;
 }
