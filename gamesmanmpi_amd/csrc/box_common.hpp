@@ -120,7 +120,7 @@ GM_HD uint32_t bx_swap_key(uint32_t code, uint32_t k) {
 // {C, swap67(C)} that lies in the root's region whole, the box with c6 > c7 is computed and
 // carries the mirror flag (it also stores its twin); the box with c6 < c7 is mirrored-to and
 // never computed.  Every other region box (c6 == c7, or the twin outside the region) is
-// computed and stored once.
+// computed and stored once.  (This is the 6/7 factor of the rule; the 4/5 factor follows.)
 constexpr uint32_t BX_MIRROR_FLAG = 0x80000000u;   // bit 31 of a compute-list entry (box ids have 20 bits)
 constexpr uint32_t BX_BOX_MASK = 0x000FFFFFu;
 GM_HD uint32_t bx_swap67(uint32_t b) {
@@ -138,6 +138,27 @@ GM_HD int bx_mirror_class(uint32_t box, uint32_t root_box) {
     const int c6 = box_coord(box, 6), c7 = box_coord(box, 7);
     if (c6 == c7 || !box_in_region(bx_swap67(box), root_box)) return 0;
     return c6 > c7 ? 1 : 2;
+}
+
+// Mirror of heaps 4 and 5, the same rule on the fields c4 (bits 8-10) and c5 (bits 11-13).
+// Heaps 4 and 5 are bits 0 and 1 of B, so row m of swap45(C) is row m of C with bytes 1 and 2 of
+// each dword exchanged (v_perm_b32 selector BX_PERM45), the row's address unchanged; through
+// both mirrors, the permuted dwords in the order {0, 2, 1, 3}.  Region membership factorises
+// over the coordinates, so a box's two classes are independent: a box is computed iff neither
+// class is 2; a computed box stores itself, swap67 of itself if its 6/7 class is 1 (bit 31 of its
+// list entry), swap45 of itself if its 4/5 class is 1 (bit 30), and swap45(swap67()) of itself
+// if both are.  Every region box is then written exactly once and nothing outside the region is.
+constexpr uint32_t BX_MIRROR45_FLAG = 0x40000000u;   // bit 30 of a compute-list entry
+constexpr uint32_t BX_PERM45 = 0x03010200u;
+GM_HD uint32_t bx_swap45(uint32_t b) {
+    const uint32_t t = ((b >> 8) ^ (b >> 11)) & 7u;
+    return b ^ (t << 8) ^ (t << 11);
+}
+GM_HD int bx_mirror_class67(uint32_t box, uint32_t root_box) { return bx_mirror_class(box, root_box); }
+GM_HD int bx_mirror_class45(uint32_t box, uint32_t root_box) {
+    const int c4 = box_coord(box, 4), c5 = box_coord(box, 5);
+    if (c4 == c5 || !box_in_region(bx_swap45(box), root_box)) return 0;
+    return c4 > c5 ? 1 : 2;
 }
 
 }  // namespace gm

@@ -39,9 +39,10 @@
 //          codes (masked at their digit boundaries) and (a3) from its codes 16 and 32
 //          steps ago (zero before its start); 73 steps, no barrier;
 //   store  16-B rows of both boxes (write-through); the one-GPU tier launches (GM_OPT_SYMMETRY
-//          1) compute only one box of each pair that differs by the exchange of heaps 6 and 7
-//          and store its rows a second time, dwords 1 and 2 exchanged, to the other
-//          (box_common.hpp): 589,824 of the 2^20 boxes computed, all stored.
+//          1) compute only one box of each pair that differs by the exchange of heaps 6 and 7,
+//          and of each pair that differs by the exchange of heaps 4 and 5, and store its rows
+//          again to the others (dwords 1 and 2 exchanged, bytes 1 and 2 of each dword
+//          exchanged, or both; box_common.hpp): 331,776 of the 2^20 boxes computed, all stored.
 // The max of up to 13 inputs uses v_pk_maximum3_f16: a code 0..255 in the low byte of
 // an f16 is a subnormal, ordered like the integer (the kernel keeps f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3).
@@ -72,7 +73,10 @@ typedef uint16_t bx_u16x2 __attribute__((ext_vector_type(2)));
 #define GM_BOX_TIER_STORE_CPOL GM_BOX_STORE_CPOL   // the tier launches' own (the dataflow kernels keep sc1)
 #endif
 #ifndef GM_BOX_MIRROR_STORE_CPOL
-#define GM_BOX_MIRROR_STORE_CPOL GM_BOX_TIER_STORE_CPOL   // the mirrored box's rows (2 = nt)
+#define GM_BOX_MIRROR_STORE_CPOL GM_BOX_TIER_STORE_CPOL   // the mirrored boxes' rows (2 = nt)
+#endif
+#ifndef GM_BOX_MIRROR_SET
+#define GM_BOX_MIRROR_SET 3    // the mirrors GM_OPT_SYMMETRY 1 uses: bit 0 heaps 6/7, bit 1 heaps 4/5
 #endif
 #ifndef GM_BOX_WAVES
 #define GM_BOX_WAVES 2         // waves per SIMD the register budget must allow
@@ -194,7 +198,8 @@ struct BxGroup {
 
 // (One-GPU tier launches: the list is a compute list, box_common.hpp, and box[k] keeps the
 // entry's BX_MIRROR_FLAG in bit 31.  Every use of box[k] before bx_store reads coordinate
-// fields or forms the 32-bit offset box << 12, which drop the bit; bx_store masks it.)
+// fields or forms the 32-bit offset box << 12, which drop the bit, and BX_MIRROR45_FLAG in bit 30
+// with it; bx_store masks them.)
 template <bool SHARD, bool FILL = true>
 __device__ __forceinline__ BxGroup bx_group(const uint32_t *__restrict__ boxes, const uint32_t *__restrict__ fills,
                                             const uint32_t *__restrict__ srcs, const uint32_t *__restrict__ dsts,
@@ -598,6 +603,16 @@ __device__ __forceinline__ void bx_walk(uint32_t *s, uint32_t ln, const BxLaneC 
     bx_unroll(step, std::make_integer_sequence<int, BX_STEPS>{});
 }
 
+// The descriptor of a mirror twin (bx_store, MIRROR).  Six more descriptors held over the rows
+// would not fit the SGPR file beside the rest, so a twin is kept as one word, its byte offset in
+// the table (a multiple of 4096) | 1 if it is stored, and its descriptor is built from that word
+// at each store (the asm keeps the compiler from hoisting the four words out of the row loop).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t bx_twin_rsrc(uint8_t *table, uint32_t t) {
+    t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);   // (uniform: a no-op unless the compiler held it in a VGPR)
+    asm volatile("" : "+s"(t));
+    return __builtin_amdgcn_make_buffer_rsrc(table + (uint64_t)(t & ~4095u), 0, (t & 1u) << 12, 0x00020000);
+}
+
 // store: rows m = lane + 64 i of both boxes, bytes regrouped per box.  Split solve: a box another
 // rank needs is also written, from the same registers, to its slot in the halo message (the
 // whole box, or only its two top layers along an A heap, rows compacted as box_pack_kernel
@@ -607,26 +622,31 @@ __device__ __forceinline__ void bx_walk(uint32_t *s, uint32_t ln, const BxLaneC 
 // so the receiver needs no unpack.
 // (NI rows per lane from row set i0: the one-wave kernel stores all four, a wave of the
 // four-wave kernel its own.)
-// MIRROR (one GPU, box_common.hpp): a box with the mirror flag is also stored, from the same
-// registers with dwords 1 and 2 of each row exchanged, to the same rows of swap67(box), which no
-// workgroup computes; a box without the flag gets a descriptor of size 0, which drops the stores.
+// MIRROR (one GPU, box_common.hpp): a box with the 6/7 mirror flag is also stored, from the same
+// registers with dwords 1 and 2 of each row exchanged, to the same rows of swap67(box); with the
+// 4/5 flag, bytes 1 and 2 of each dword exchanged, to swap45(box); with both, both permutations,
+// to swap45(swap67(box)).  No workgroup computes those boxes.  A twin whose flag is absent gets a
+// descriptor of size 0, which drops its stores (bx_twin_rsrc).
 template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI = 4, bool MIRROR = false>
 __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *p0, uint8_t *p1, uint8_t *p2,
                                          const BxGroup &G, const uint32_t *s, uint32_t lane, uint32_t i0 = 0) {
     constexpr bool SHARD = SHARD_ && !(GM_BOX_EXP & 32);
     static_assert(!(MIRROR && SHARD_), "the mirrored store is the one-GPU tier launches'");
-    __amdgpu_buffer_rsrc_t w[2], wx[2];
+    __amdgpu_buffer_rsrc_t w[2];
+    uint32_t tw[2][3] = {{0, 0, 0}, {0, 0, 0}};   // MIRROR: the twins of box k (bx_twin_rsrc)
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         // (MIRROR: box[k] is a compute-list entry, its flag in bit 31, masked here where it
         // becomes an address)
         const uint32_t box = MIRROR ? G.box[k] & BX_BOX_MASK : G.box[k];
-        w[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)box << 12), 0,
-                                                 (G.valid[k] && !(GM_BOX_EXP & 4)) ? 4096u : 0u, 0x00020000);
+        const bool on = G.valid[k] && !(GM_BOX_EXP & 4);
+        w[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)box << 12), 0, on ? 4096u : 0u, 0x00020000);
         if constexpr (MIRROR) {
-            const bool mir = G.valid[k] && (G.box[k] & BX_MIRROR_FLAG);
-            wx[k] = __builtin_amdgcn_make_buffer_rsrc(table + ((uint64_t)bx_swap67(box) << 12), 0,
-                                                      (mir && !(GM_BOX_EXP & 4)) ? 4096u : 0u, 0x00020000);
+            const uint32_t m67 = (on && (G.box[k] & BX_MIRROR_FLAG)) ? 1u : 0u;
+            const uint32_t m45 = (on && (G.box[k] & BX_MIRROR45_FLAG)) ? 1u : 0u;
+            tw[k][0] = (bx_swap67(box) << 12) | m67;
+            tw[k][1] = (bx_swap45(box) << 12) | m45;
+            tw[k][2] = (bx_swap45(bx_swap67(box)) << 12) | (m67 & m45);
         }
     }
     uint32_t dst[2][3] = {{0, 0, 0}, {0, 0, 0}};
@@ -654,9 +674,21 @@ __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *
         __builtin_amdgcn_raw_buffer_store_b128(o[1], w[1], 16u * m, 0, CP);
         if constexpr (MIRROR) {
 #pragma unroll
-            for (int k = 0; k < 2; k++)
-                __builtin_amdgcn_raw_buffer_store_b128(bx_u32x4{o[k][0], o[k][2], o[k][1], o[k][3]}, wx[k], 16u * m, 0,
-                                                       GM_BOX_MIRROR_STORE_CPOL);
+            for (int k = 0; k < 2; k++) {
+                constexpr int MC = GM_BOX_MIRROR_STORE_CPOL;
+                if constexpr (GM_BOX_MIRROR_SET & 1)
+                    __builtin_amdgcn_raw_buffer_store_b128(bx_u32x4{o[k][0], o[k][2], o[k][1], o[k][3]},
+                                                           bx_twin_rsrc(table, tw[k][0]), 16u * m, 0, MC);
+                if constexpr (GM_BOX_MIRROR_SET & 2) {
+                    bx_u32x4 p;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) p[q] = __builtin_amdgcn_perm(o[k][q], o[k][q], BX_PERM45);
+                    __builtin_amdgcn_raw_buffer_store_b128(p, bx_twin_rsrc(table, tw[k][1]), 16u * m, 0, MC);
+                    if constexpr (GM_BOX_MIRROR_SET & 1)
+                        __builtin_amdgcn_raw_buffer_store_b128(bx_u32x4{p[0], p[2], p[1], p[3]},
+                                                               bx_twin_rsrc(table, tw[k][2]), 16u * m, 0, MC);
+                }
+            }
         }
         if constexpr (SHARD && DIRECT) {
 #pragma unroll
@@ -712,8 +744,8 @@ __device__ unsigned long long bx_trace_acc[8];
 // per box saying where each child box is read from.
 // FILL (split solve): some box of the launch reads a child through a transposition; a launch
 // without (every tier of rank 0, most of the others' first tiers) reads its children as at N = 1.
-// MIRROR (one GPU): `boxes` is the tier's compute list (box_common.hpp), and a box with the mirror
-// flag is stored twice (bx_store).
+// MIRROR (one GPU): `boxes` is the tier's compute list (box_common.hpp), and a box with mirror
+// flags is stored two or four times (bx_store).
 template <bool SHARD, bool DIRECT = false, bool FILL = true, bool MIRROR = !SHARD>
 __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_tier_kernel(uint8_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ boxes,
@@ -1446,7 +1478,8 @@ struct DenseBox {
     std::vector<uint32_t> tier_off;
     std::vector<uint32_t> boxes;      // host copy (digest list = every box of the region)
     // the tier launches' compute list (box_common.hpp): the full list without the mirrored-to
-    // boxes, same order, entries box | BX_MIRROR_FLAG; the full list itself with the mirror off
+    // boxes, same order, entries box | BX_MIRROR_FLAG | BX_MIRROR45_FLAG; the full list itself
+    // with the mirror off
     bool mirror = false;              // GM_OPT_SYMMETRY when the lists were built
     uint32_t *d_cboxes = nullptr;
     std::vector<uint32_t> ctier_off;
@@ -1545,9 +1578,10 @@ static void box_region_tiers(uint32_t root_hi, std::vector<uint32_t> &boxes, std
     }
 }
 
-// The compute list of a full list (box_common.hpp bx_mirror_class): the mirrored-to boxes
-// dropped, the order (Hilbert inside a tier) kept, so the kernel's 8 XCD runs are runs of the
-// same walk; mirror off: the full list, no flags.
+// The compute list of a full list (box_common.hpp bx_mirror_class67 / 45, the mirrors of
+// GM_BOX_MIRROR_SET): the boxes mirrored-to through either dropped, the order (Hilbert inside a
+// tier) kept, so the kernel's 8 XCD runs are runs of the same walk; mirror off: the full list, no
+// flags.
 void box_compute_list(uint32_t root_hi, bool mirror, const std::vector<uint32_t> &boxes,
                       const std::vector<uint32_t> &tier_off, std::vector<uint32_t> &cboxes,
                       std::vector<uint32_t> &ctier_off) {
@@ -1555,8 +1589,10 @@ void box_compute_list(uint32_t root_hi, bool mirror, const std::vector<uint32_t>
     ctier_off.assign(1, 0);
     for (size_t t = 0; t + 1 < tier_off.size(); t++) {
         for (uint32_t i = tier_off[t]; i < tier_off[t + 1]; i++) {
-            const int cls = mirror ? bx_mirror_class(boxes[i], root_hi) : 0;
-            if (cls != 2) cboxes.push_back(boxes[i] | (cls == 1 ? BX_MIRROR_FLAG : 0u));
+            const int c67 = (mirror && (GM_BOX_MIRROR_SET & 1)) ? bx_mirror_class67(boxes[i], root_hi) : 0;
+            const int c45 = (mirror && (GM_BOX_MIRROR_SET & 2)) ? bx_mirror_class45(boxes[i], root_hi) : 0;
+            if (c67 != 2 && c45 != 2)
+                cboxes.push_back(boxes[i] | (c67 == 1 ? BX_MIRROR_FLAG : 0u) | (c45 == 1 ? BX_MIRROR45_FLAG : 0u));
         }
         ctier_off.push_back((uint32_t)cboxes.size());
     }

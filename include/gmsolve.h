@@ -120,10 +120,13 @@ enum {
                                per left-right mirror pair when the root is its own mirror image; every
                                count, export, query and digest still covers both positions.  0 = off.
                                Box engine (SUBTRACT, 8 heaps, one GPU, tier launches): 1 (default) = of
-                               two boxes that differ by the exchange of heaps 6 and 7 one is computed
-                               and both are stored (the other's rows are the same rows with dwords 1
-                               and 2 exchanged); every position is still stored, so n_stored stays
-                               n_positions and gm_verify checks them all.  0 = every box computed.
+                               two boxes that differ by the exchange of heaps 6 and 7, and of two that
+                               differ by the exchange of heaps 4 and 5, one is computed and both are
+                               stored, so a computed box stores up to four (a twin's rows are the same
+                               rows with dwords 1 and 2, or bytes 1 and 2 of each dword, exchanged;
+                               the build option GM_BOX_MIRROR_SET keeps one pair of heaps only); every
+                               position is still stored, so n_stored stays n_positions and gm_verify
+                               checks them all.  0 = every box computed.
                                Changing it between solves rebuilds the box lists and the graph */
     GM_OPT_BOX_FLOW = 15,   /* box engine (SUBTRACT, 8 heaps), one GPU: -1 (default) / 0 = one launch per
                                box-tier; 1 = one dataflow launch (box_flow_kernel: a box group starts

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Per-box-tier times of the one-GPU 2^32 solve from a rocprofv3 kernel trace.
 
-    python tools/box_tier_trace.py <trace dir> [--json out.json] [--mirror] [--last N]
+    python tools/box_tier_trace.py <trace dir> [--json out.json] [--mirror [SET]] [--last N]
 
---mirror: the groups of the compute list (GM_OPT_SYMMETRY 1: of the boxes that differ by the
-exchange of heaps 6 and 7 only the one with c6 >= c7 is computed); --last N: the last N solves
-of the trace only (the bench's timed solves, without its warm-up).
+--mirror: the groups of the compute list (GM_OPT_SYMMETRY 1), SET as GM_BOX_MIRROR_SET: 1 (the
+default of the flag alone) = of the boxes that differ by the exchange of heaps 6 and 7 only the
+one with c6 >= c7 is computed, 3 = also only c4 >= c5 of heaps 4 and 5; --last N: the last N
+solves of the trace only (the bench's timed solves, without its warm-up).
 
 The trace is of `bench.py` (one GPU, box engine): every solve is 41 launches of
 box_tier_kernel<false>, box-tier 0 first.  Per box-tier: its groups (two boxes each: the boxes
@@ -23,11 +24,15 @@ import json
 import numpy as np
 
 
-def tier_groups(mirror=False):
+def tier_groups(mirror=0):
     b = np.arange(1 << 20)
     t = sum((b >> (2 * i)) & 3 for i in range(4)) + sum((b >> (8 + 3 * j)) & 7 for j in range(4))
-    if mirror:
-        t = t[((b >> 14) & 7) >= ((b >> 17) & 7)]
+    keep = np.ones(1 << 20, bool)
+    if mirror & 1:
+        keep &= ((b >> 14) & 7) >= ((b >> 17) & 7)
+    if mirror & 2:
+        keep &= ((b >> 8) & 7) >= ((b >> 11) & 7)
+    t = t[keep]
     n = np.bincount(t, minlength=41)
     return (n + 1) // 2
 
@@ -37,7 +42,8 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--json", default=None)
     ap.add_argument("--round", type=int, default=2048, help="groups per resident round")
-    ap.add_argument("--mirror", action="store_true", help="groups of the heap-6/7 mirror's compute list")
+    ap.add_argument("--mirror", type=int, nargs="?", const=1, default=0,
+                    help="groups of the mirrors' compute list (GM_BOX_MIRROR_SET; alone: 1, heaps 6/7)")
     ap.add_argument("--last", type=int, default=0, help="use only the last N solves (0: all)")
     a = ap.parse_args()
     rows = []

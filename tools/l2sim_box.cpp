@@ -12,7 +12,9 @@
 // mirror = 1 (csrc/box_common.hpp, the one-GPU tier launches with GM_OPT_SYMMETRY 1): of each
 // pair of boxes that differ by the exchange of dimensions 6 and 7, only the box with c6 >= c7
 // is computed -- only its child reads are replayed, in the tier's order without the others --
-// and a box with c6 > c7 also writes its twin.
+// and a box with c6 > c7 also writes its twin.  mirror = 2: the same on dimensions 4 and 5 as
+// well (computed: c6 >= c7 and c4 >= c5); a box writes its twin through each mirror it leads and
+// through both.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -134,7 +136,12 @@ int main(int argc, char **argv) {
         peak_t = std::max<uint64_t>(peak_t, t.size());
         std::stable_sort(t.begin(), t.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
         if (mirror)   // the compute list: the mirrored-to boxes dropped, the order kept
-            t.erase(std::remove_if(t.begin(), t.end(), [&](uint32_t b) { int c[8]; coords(b, c); return c[6] < c[7]; }),
+            t.erase(std::remove_if(t.begin(), t.end(),
+                                   [&](uint32_t b) {
+                                       int c[8];
+                                       coords(b, c);
+                                       return c[6] < c[7] || (mirror >= 2 && c[4] < c[5]);
+                                   }),
                     t.end());
         ncomp += t.size();
         const uint32_t ng = (t.size() + K - 1) / K;
@@ -179,10 +186,16 @@ int main(int argc, char **argv) {
                     }
                     int c[8];
                     coords(t[idx], c);
-                    if (mirror && c[6] > c[7]) {   // the twin's rows, written by the same group
-                        std::swap(c[6], c[7]);
-                        const uint64_t tw = index(c);
-                        for (int qd = 0; qd < nchunks; qd++) mall.touch(tw * nchunks + qd);
+                    // the twins' rows, written by the same group: through 6/7, through 4/5, through both
+                    const bool m67 = mirror && c[6] > c[7], m45 = mirror >= 2 && c[4] > c[5];
+                    for (int tw = 1; tw < 4; tw++) {
+                        if (((tw & 1) && !m67) || ((tw & 2) && !m45)) continue;
+                        int e[8];
+                        for (int i = 0; i < 8; i++) e[i] = c[i];
+                        if (tw & 1) std::swap(e[6], e[7]);
+                        if (tw & 2) std::swap(e[4], e[5]);
+                        const uint64_t tb = index(e);
+                        for (int qd = 0; qd < nchunks; qd++) mall.touch(tb * nchunks + qd);
                     }
                 }
             }
