@@ -46,11 +46,7 @@
 // The max of up to 13 inputs uses v_pk_maximum3_f16: a code 0..255 in the low byte of
 // an f16 is a subnormal, ordered like the integer (the kernel keeps f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3).
-#include "gm_internal.hpp"
-#include "hist_common.hpp"
-#include "verify_common.hpp"
-#include "moves_common.hpp"
-#include "select_common.hpp"
+#include "byte_tables.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -1327,46 +1323,6 @@ __global__ void box_epoch_kernel(uint32_t *epoch) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *epoch += 1u;
 }
 
-// digest of the positions of a box list that lie in the root's region
-__global__ void box_digest_kernel(const uint8_t *__restrict__ table, const uint32_t *__restrict__ boxes, uint64_t nbox,
-                                  uint64_t root, unsigned long long *acc) {
-    uint64_t sum = 0, cnt = 0;
-    for (uint64_t x = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; x < (nbox << 12);
-         x += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t idx = (boxes[x >> 12] << 12) | (uint32_t)(x & 4095u);
-        const uint32_t k = box_key_of_index(idx);
-        bool in = true;
-        for (int j = 0; j < 8; j++) in &= ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-        if (!in) continue;
-        sum += digest_term(k, record_of_code(table[idx]));
-        cnt++;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_xor(sum, o);
-        cnt += __shfl_xor(cnt, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(acc, (unsigned long long)sum);
-        atomicAdd(acc + 1, (unsigned long long)cnt);
-    }
-}
-
-// Records of keys: REC_UNSOLVED outside the root's region (a key with a nibble above the
-// root's, whose slot the solve never wrote).  Split solve with virtual ranks (dist_box.hip):
-// `owner` gives per box id the rank whose table holds it (0xFF: none), `tables` per rank.
-__global__ void box_query_kernel(const uint8_t *const *__restrict__ tables, const uint8_t *__restrict__ owner,
-                                 uint64_t root, const uint64_t *__restrict__ keys, uint16_t *__restrict__ out, uint64_t n) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t k = keys[i];
-    bool in = k < (1ull << 32);
-    for (int j = 0; j < 8 && in; j++) in = ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-    if (!in) { out[i] = REC_UNSOLVED; return; }
-    const uint32_t idx = box_index_of_key((uint32_t)k);
-    const uint32_t r = owner ? owner[idx >> 12] : 0u;
-    out[i] = r == 0xFFu ? REC_UNSOLVED : record_of_code(tables[r][idx]);
-}
-
 // ---------------------------------------------------------------------------
 // host
 
@@ -1460,15 +1416,6 @@ int box_split_flow_resident(int device) {
     return std::min(box_resident((const void *)box_split_flow_kernel<true>, device, 0),
                     box_resident((const void *)box_split_flow_kernel<false>, device, 0));
 }
-void box_launch_digest(const uint8_t *table, const uint32_t *boxes, uint64_t nbox, uint64_t root,
-                       unsigned long long *acc, hipStream_t s) {
-    if (nbox) hipLaunchKernelGGL(box_digest_kernel, dim3(4096), dim3(256), 0, s, table, boxes, nbox, root, acc);
-}
-void box_launch_query(const uint8_t *const *tables, const uint8_t *owner, uint64_t root, const uint64_t *keys,
-                      uint16_t *out, uint64_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(box_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tables, owner, root, keys,
-                              out, n);
-}
 
 struct DenseBox {
     uint32_t root_hi = 0;
@@ -1487,8 +1434,7 @@ struct DenseBox {
     hipStream_t graph_stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     int grid_cap = 2048;
-    uint64_t *d_acc = nullptr;
-    const uint8_t **d_tables = nullptr;   // [1] = table (box_query_kernel's table array)
+    const uint8_t **d_tables = nullptr;   // [1] = table (byte_tables.hpp)
     bool flow = false;                // one-launch (dataflow) solve (GM_OPT_BOX_FLOW)
     int flow_grid = 0;                // the dataflow launch's grid: its resident capacity
     size_t flow_dyn = 0;              // dynamic LDS of the dataflow launch (GM_BOX_FLOW_EXTRA_LDS, tests)
@@ -1603,7 +1549,6 @@ static void dense_box_free(Ctx *c);
 // A half-built context is never kept: every failure path frees it.
 static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     d->root_hi = box_index_of_key((uint32_t)root) >> 12;
-    GM_HIP(hipMalloc(&d->d_acc, 2 * sizeof(uint64_t)));
     d->grid_cap = box_resident((const void *)box_tier_kernel<false>, c->device, 0);
     const uint64_t bytes = 1ull << 32;
     if (c->adopted_dense && c->adopted_dense_bytes < bytes) {
@@ -1832,11 +1777,14 @@ static int dense_box_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-static int dense_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+// The read side (byte_tables.hpp): one table, box-indexed, the region's boxes of 4 KiB each.
+static void dense_box_bytes(Ctx *c, ByteTables *t) {
     DenseBox *d = c->dbox;
-    return query_keys(c, keys, recs, n, BOX_QUERY_CHUNK, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
-        box_launch_query(d->d_tables, nullptr, c->root, dk, dr, m, c->stream);
-    });
+    t->box = 1;
+    t->heaps = 8;
+    t->ushift = 12;
+    t->d_tables = d->d_tables;
+    t->parts = {{d->table, d->d_boxes, d->boxes.size()}};
 }
 
 // keys of the root's region in ascending order (heap 0 fastest)
@@ -1864,7 +1812,7 @@ static int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
         return GM_E_CAP;
     }
     box_region_keys(c->root, keys, c->n_positions);
-    if (c->n_positions <= BOX_QUERY_CHUNK) return dense_box_query(c, keys, recs, c->n_positions);
+    if (c->n_positions <= BOX_QUERY_CHUNK) return byte_query(c, keys, recs, c->n_positions);
     // large regions: one copy of the table, decoded on the host
     std::vector<uint8_t> tab(1ull << 32);
     GM_HIP(hipMemcpy(tab.data(), d->table, tab.size(), hipMemcpyDeviceToHost));
@@ -1872,63 +1820,9 @@ static int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
     return GM_OK;
 }
 
-static int dense_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    DenseBox *d = c->dbox;
-    GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
-    box_launch_digest(d->table, d->d_boxes, d->boxes.size(), c->root, (unsigned long long *)d->d_acc, c->stream);
-    GM_HIP(hipGetLastError());
-    uint64_t hst[2];
-    GM_HIP(hipMemcpyAsync(hst, d->d_acc, 16, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    *digest = hst[0];
-    *n = hst[1];
-    return GM_OK;
-}
-
-// census of the region's boxes (hist_common.hpp)
-static int dense_box_histogram(Ctx *c, Hist *out) {
-    DenseBox *d = c->dbox;
-    CodeBins b;
-    GM_TRY(code_bins_begin(c, &b));
-    int rc = code_bins_launch<1>(c, &b, d->table, d->d_boxes, d->boxes.size(), 12, 8);
-    const int rc2 = code_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
-}
-
-// gm_select over the same boxes (select_common.hpp)
-static int dense_box_select(Ctx *c, const SelectDev &s) {
-    DenseBox *d = c->dbox;
-    return byte_select_launch<1>(c, s, d->table, d->d_boxes, d->boxes.size(), 12, 8);
-}
-
 static int dense_box_table(Ctx *c, void **p, uint64_t *bytes) {
     *p = c->dbox->table;
     *bytes = 1ull << 32;
-    return GM_OK;
-}
-
-// gm_moves: every code at box_index_of_key of its key (moves_common.hpp)
-static int dense_box_moves(Ctx *c, const MovesReq &r) {
-    DenseBox *d = c->dbox;
-    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<1>(c, mv, d->d_tables, nullptr, 0, 8); });
-}
-
-// gm_verify over the region's boxes, each 4 KiB of the table (verify_common.hpp)
-static int dense_box_verify(Ctx *c, const VerifyDev &v) {
-    DenseBox *d = c->dbox;
-    return byte_verify_launch<1>(c, v, d->d_tables, nullptr, d->d_boxes, d->boxes.size(), 12, 0, 8);
-}
-
-static int dense_box_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    DenseBox *d = c->dbox;
-    bool in = words[0] < (1ull << 32);
-    for (int j = 0; j < 8 && in; j++) in = ((words[0] >> (4 * j)) & 15u) <= ((c->root >> (4 * j)) & 15u);
-    if (!in) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-    const int code = code_of_record(rec);
-    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
-    const uint8_t b = (uint8_t)code;
-    GM_HIP(hipMemcpyAsync(d->table + box_index_of_key((uint32_t)words[0]), &b, 1, hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
     return GM_OK;
 }
 
@@ -1939,7 +1833,7 @@ static void dense_box_free(Ctx *c) {
     for (auto e : d->ev)
         if (e) (void)hipEventDestroy(e);
     if (d->owned && d->table) (void)hipFree(d->table);
-    for (void *q : {(void *)d->d_boxes, (void *)d->d_cboxes, (void *)d->d_groups, (void *)d->d_acc, (void *)d->d_flow, (void *)d->d_tables})
+    for (void *q : {(void *)d->d_boxes, (void *)d->d_cboxes, (void *)d->d_groups, (void *)d->d_flow, (void *)d->d_tables})
         if (q) (void)hipFree(q);
     if (d->h_res) (void)hipHostFree(d->h_res);
     delete d;
@@ -1947,7 +1841,7 @@ static void dense_box_free(Ctx *c) {
 }
 
 GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
-                 dense_box_query, dense_box_digest, dense_box_histogram, dense_box_select, dense_box_table, dense_box_free,
-                 dense_box_verify, dense_box_poke, nullptr, dense_box_moves)
+                 byte_query, byte_digest, byte_histogram, byte_select, dense_box_table, dense_box_free,
+                 byte_verify, byte_poke, nullptr, byte_moves, dense_box_bytes)
 
 }  // namespace gm

@@ -32,11 +32,7 @@
 // HBM bytes per position: 1 written + 1 per high child (1.8125 per high nibble
 // on average).  The SURVEY §8d edge model charges 1 B per record and per child
 // edge: 1 + 14.5 = 15.5 B per position at 8 heaps (31 B with u16 records).
-#include "gm_internal.hpp"
-#include "hist_common.hpp"
-#include "verify_common.hpp"
-#include "moves_common.hpp"
-#include "select_common.hpp"
+#include "byte_tables.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -60,7 +56,7 @@ struct DenseSub {
     uint32_t *d_blocks = nullptr;       // high parts of the root box, sorted by (tier, order)
     uint32_t box = 0;                   // the root's high part: blocks with every nibble <= its
     std::vector<uint32_t> tier_off;     // block offsets per high tier
-    uint64_t *d_acc = nullptr;          // digest / counters
+    const uint8_t **d_tables = nullptr; // [1] = table (byte_tables.hpp)
     hipGraphExec_t graph = nullptr;
     hipStream_t graph_stream = nullptr;
     std::vector<hipEvent_t> ev;         // timing events
@@ -898,42 +894,6 @@ int sub_kernel_threads(const Ctx *c, int low) {
 }
 
 // ---------------------------------------------------------------------------
-__global__ void sub_digest_kernel(const uint8_t *__restrict__ table, uint64_t slots, int heaps,
-                                  uint64_t root, unsigned long long *acc) {
-    uint64_t sum = 0, cnt = 0;
-    for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < slots;
-         k += (uint64_t)gridDim.x * blockDim.x) {
-        bool in = true;
-        for (int j = 0; j < heaps; j++) in &= ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-        if (!in) continue;
-        const uint8_t code = table[k];
-        if (!code) continue;   // a position an imported table does not hold (a solve fills the region)
-        sum += digest_term(k, record_of_code(code));
-        cnt++;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_xor(sum, o);
-        cnt += __shfl_xor(cnt, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(acc, (unsigned long long)sum);
-        atomicAdd(acc + 1, (unsigned long long)cnt);
-    }
-}
-
-// a key outside the root's region (a heap above the root's) answers REC_UNSOLVED: the slot
-// may hold an earlier solve's code (include/gmsolve.h gm_query)
-__global__ void sub_query_kernel(const uint8_t *__restrict__ table, uint64_t slots, uint64_t root, int heaps,
-                                 const uint64_t *__restrict__ keys, uint16_t *__restrict__ out, uint64_t n) {
-    uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t k = keys[i];
-    bool in = k < slots;
-    for (int j = 0; j < heaps && in; j++) in = ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-    out[i] = in ? record_of_code(table[k]) : REC_UNSOLVED;
-}
-
-// ---------------------------------------------------------------------------
 // Morton (bit-interleaved) code of a high part's nibbles.  Sorting each tier by it
 // keeps the five same-tier parents of a child block (one high nibble +1 each) close
 // in the launch order, hence on the same XCD at about the same time: their shared
@@ -991,11 +951,7 @@ void sort_tiers_morton(std::vector<uint32_t> &order, const std::vector<uint32_t>
 // (positions of a needed block beyond the root's low nibbles are solved too: they
 // are exact, only not counted or exported).
 static uint32_t root_box(const DenseSub *d, uint64_t root) { return (uint32_t)(root >> (4 * d->low)); }
-static bool in_box(uint32_t v, uint32_t box, int high) {
-    for (int j = 0; j < high; j++)
-        if (((v >> (4 * j)) & 15u) > ((box >> (4 * j)) & 15u)) return false;
-    return true;
-}
+static bool in_box(uint32_t v, uint32_t box, int high) { return sub_in_region(v, box, high); }
 
 static int prepare(Ctx *c, DenseSub *d, uint64_t root) {
     int heaps = c->sub.heaps;
@@ -1030,7 +986,6 @@ static int prepare(Ctx *c, DenseSub *d, uint64_t root) {
     size_t zbytes = std::max<size_t>(16, (size_t)1 << (4 * low));
     GM_HIP(hipMalloc(&d->zero, zbytes));
     GM_HIP(hipMemset(d->zero, 0, zbytes));
-    GM_HIP(hipMalloc(&d->d_acc, 2 * sizeof(uint64_t)));
     uint64_t bytes = d->slots;
     if (c->adopted_dense) {
         if (c->adopted_dense_bytes < bytes) {
@@ -1047,6 +1002,8 @@ static int prepare(Ctx *c, DenseSub *d, uint64_t root) {
         }
         d->owned = true;
     }
+    GM_HIP(hipMalloc(&d->d_tables, sizeof(uint8_t *)));
+    GM_HIP(hipMemcpy(d->d_tables, &d->table, sizeof(uint8_t *), hipMemcpyHostToDevice));
     return GM_OK;
 }
 
@@ -1203,9 +1160,7 @@ static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
     GM_HIP(hipMemcpy(h.data(), d->table, d->slots, hipMemcpyDeviceToHost));
     uint64_t j = 0;
     for (uint64_t k = 0; k < d->slots; k++) {
-        bool in = true;
-        for (int i = 0; i < d->heaps && in; i++) in = ((k >> (4 * i)) & 15u) <= ((c->root >> (4 * i)) & 15u);
-        if (!in || !h[k] || j >= cap) continue;   // code 0: a position an imported table does not hold
+        if (!sub_in_region(k, c->root, d->heaps) || !h[k] || j >= cap) continue;   // code 0: a position an imported table does not hold
         keys[j] = k;
         recs[j] = record_of_code(h[k]);
         j++;
@@ -1213,89 +1168,21 @@ static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
     return GM_OK;
 }
 
-static int dense_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+// The read side (byte_tables.hpp): one table, slot = key, one unit of 16^heaps bytes.  Code 0 in
+// the region is a position an imported table does not hold (a solve fills the region).
+static void dense_sub_bytes(Ctx *c, ByteTables *t) {
     DenseSub *d = c->dsub;
-    return query_keys(c, keys, recs, n, n, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
-        hipLaunchKernelGGL(sub_query_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, d->table,
-                           d->slots, c->root, c->sub.heaps, dk, dr, m);
-    });
-}
-
-static int dense_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    DenseSub *d = c->dsub;
-    GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
-    hipLaunchKernelGGL(sub_digest_kernel, dim3(2048), dim3(256), 0, c->stream, d->table, d->slots, d->heaps, c->root,
-                       (unsigned long long *)d->d_acc);
-    uint64_t h[2];
-    GM_HIP(hipMemcpyAsync(h, d->d_acc, 16, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    *digest = h[0];
-    *n = h[1];
-    return GM_OK;
-}
-
-// census of the root's region: the table is one unit of 16^heaps bytes, slot = key
-static int dense_sub_histogram(Ctx *c, Hist *out) {
-    DenseSub *d = c->dsub;
-    CodeBins b;
-    GM_TRY(code_bins_begin(c, &b));
-    int rc = code_bins_launch<0>(c, &b, d->table, nullptr, 1, 4 * d->heaps, d->heaps);
-    const int rc2 = code_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
-}
-
-// gm_select over the root's region, one unit of 16^heaps bytes (select_common.hpp)
-static int dense_sub_select(Ctx *c, const SelectDev &s) {
-    DenseSub *d = c->dsub;
-    return byte_select_launch<0>(c, s, d->table, nullptr, 1, 4 * d->heaps, d->heaps);
+    t->heaps = d->heaps;
+    t->ushift = 4 * d->heaps;
+    t->skip_empty = true;
+    t->d_tables = d->d_tables;
+    t->parts = {{d->table, nullptr, 1}};
 }
 
 static int dense_sub_table(Ctx *c, void **p, uint64_t *bytes) {
     DenseSub *d = c->dsub;
     *p = d->table;
     *bytes = d->slots;
-    return GM_OK;
-}
-
-// gm_verify: the table is one unit of 16^heaps bytes, slot = key (verify_common.hpp)
-static int dense_sub_verify(Ctx *c, const VerifyDev &v) {
-    DenseSub *d = c->dsub;
-    DevBuf<const uint8_t *> tabs;
-    GM_TRY(tabs.alloc(1));
-    const uint8_t *t = d->table;
-    GM_HIP(hipMemcpyAsync(tabs, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
-    GM_TRY(byte_verify_launch<0>(c, v, tabs.p, nullptr, nullptr, 1, 4 * d->heaps, 0, d->heaps));
-    GM_HIP(hipStreamSynchronize(c->stream));   // tabs leaves scope
-    return GM_OK;
-}
-
-// gm_moves: slot = key in the one table (moves_common.hpp)
-static int dense_sub_moves(Ctx *c, const MovesReq &r) {
-    DenseSub *d = c->dsub;
-    DevBuf<const uint8_t *> tabs;
-    GM_TRY(tabs.alloc(1));
-    const uint8_t *t = d->table;
-    GM_HIP(hipMemcpyAsync(tabs, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));   // t leaves scope
-    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<0>(c, mv, tabs.p, nullptr, 0, d->heaps); });
-}
-
-// a key of the root's region of a SUBTRACT table of `heaps` heaps
-static bool sub_key_held(const Ctx *c, uint64_t k, int heaps) {
-    if (heaps < 16 && (k >> (4 * heaps))) return false;
-    for (int j = 0; j < heaps; j++)
-        if (((k >> (4 * j)) & 15u) > ((c->root >> (4 * j)) & 15u)) return false;
-    return true;
-}
-
-static int dense_sub_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    DenseSub *d = c->dsub;
-    if (!sub_key_held(c, words[0], d->heaps)) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-    const int code = code_of_record(rec);
-    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
-    const uint8_t b = (uint8_t)code;
-    GM_HIP(hipMemcpyAsync(d->table + words[0], &b, 1, hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
     return GM_OK;
 }
 
@@ -1307,7 +1194,7 @@ static void dense_sub_free(Ctx *c) {
     if (d->owned && d->table) (void)hipFree(d->table);
     if (d->zero) (void)hipFree(d->zero);
     if (d->d_blocks) (void)hipFree(d->d_blocks);
-    if (d->d_acc) (void)hipFree(d->d_acc);
+    if (d->d_tables) (void)hipFree(d->d_tables);
     delete d;
     c->dsub = nullptr;
 }
@@ -1328,10 +1215,8 @@ __global__ __launch_bounds__(256) void sub_import_kernel(uint8_t *table, uint64_
         if (k >= slots) {
             why = SUBIMP_INVALID;
         } else {
-            bool in = true;
-            for (int j = 0; j < heaps; j++) in &= ((k >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
             const uint32_t val = rec >> 14, rem = rec & 0x3FFFu;
-            if (!in) why = SUBIMP_REGION;
+            if (!sub_in_region(k, root, heaps)) why = SUBIMP_REGION;
             else if (rec == REC_UNSOLVED || rem > 126u || val > (uint32_t)LOSS) why = SUBIMP_RECORD;   // gm_poke's rule
             else {
                 const uint32_t code = val == (uint32_t)WIN ? rem + 1u : 255u - rem, sh = 8u * (uint32_t)(k & 3u);
@@ -1393,7 +1278,7 @@ static int dense_sub_import(Ctx *c, const void *keys_, const uint16_t *recs, uin
 }
 
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
-                 dense_sub_query, dense_sub_digest, dense_sub_histogram, dense_sub_select, dense_sub_table, dense_sub_free,
-                 dense_sub_verify, dense_sub_poke, dense_sub_import, dense_sub_moves)
+                 byte_query, byte_digest, byte_histogram, byte_select, dense_sub_table, dense_sub_free,
+                 byte_verify, byte_poke, dense_sub_import, byte_moves, dense_sub_bytes)
 
 }  // namespace gm

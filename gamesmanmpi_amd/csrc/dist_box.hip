@@ -42,11 +42,7 @@
 // wait; gm_box_plan shows it on the host); virtual ranks run theirs on per-rank streams and
 // tables, enqueued by a host scheduler that interleaves the lists so that every cross-rank wait
 // comes after the record it waits for.
-#include "gm_internal.hpp"
-#include "hist_common.hpp"
-#include "verify_common.hpp"
-#include "moves_common.hpp"
-#include "select_common.hpp"
+#include "byte_tables.hpp"
 #include "gm_common.hpp"
 #include "box_common.hpp"
 
@@ -584,9 +580,8 @@ struct DistBox {
     int want_batch = 0, want_sym = 0, want_split = 0, want_poison = 0;
     std::vector<BxRank> ranks;            // the ranks this context runs
     int grid_cap = 2048;
-    unsigned long long *d_acc = nullptr;
     uint32_t *d_root = nullptr;
-    uint8_t *d_owner = nullptr;           // per box id: index into d_tables of its holder (0xFF: none)
+    uint8_t *d_owner = nullptr;          // per box id: index into d_tables of its holder (0xFF: none)
     const uint8_t **d_tables = nullptr;
     hipEvent_t ev_fork = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     ncclComm_t comm[3] = {};
@@ -813,7 +808,6 @@ static int bx_prepare(Ctx *c, DistBox *d, uint64_t root, int G, bool loopback) {
             GM_HIP(hipMemset(d->d_scratch, 0, 16));
         }
     }
-    GM_HIP(hipMalloc(&d->d_acc, 16));
     GM_HIP(hipMalloc(&d->d_root, 4));
     GM_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
     GM_HIP(hipEventCreate(&d->ev_t0));
@@ -1428,11 +1422,19 @@ static int dist_box_solve(Ctx *c, uint64_t root) {
 }
 
 // ---------------------------------------------------------------------------- results
-static int dist_box_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+// The read side (byte_tables.hpp): box-indexed tables, one per rank of this context that holds
+// one (d_tables, in the order of `ranks`), each with the boxes its rank computed; d_owner names
+// per box id the table that holds it.  Every virtual rank together is the root's region; a
+// rank of a multi-process solve reads its own boxes only.
+static void dist_box_bytes(Ctx *c, ByteTables *t) {
     DistBox *d = c->dist_box;
-    return query_keys(c, keys, recs, n, BOX_QUERY_CHUNK, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
-        box_launch_query(d->d_tables, d->d_owner, c->root, dk, dr, m, c->stream);
-    });
+    t->box = 1;
+    t->heaps = 8;
+    t->ushift = 12;
+    t->d_tables = d->d_tables;
+    t->d_owner = d->d_owner;
+    for (auto &R : d->ranks)
+        if (R.table) t->parts.push_back({R.table, R.d_boxes, R.boxes.size()});
 }
 
 // Export: every virtual rank together = the root's region; a rank of a multi-process solve:
@@ -1447,15 +1449,13 @@ static int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap,
             return GM_E_CAP;
         }
         box_region_keys(c->root, keys, c->n_positions);
-        return dist_box_query(c, keys, recs, c->n_positions);
+        return byte_query(c, keys, recs, c->n_positions);
     }
     std::vector<uint64_t> ks;
     for (uint32_t b : d->ranks[0].boxes)
         for (uint32_t o = 0; o < 4096; o++) {
             const uint32_t k = box_key_of_index((b << 12) | o);
-            bool in = true;
-            for (int i = 0; i < 8 && in; i++) in = ((k >> (4 * i)) & 15u) <= ((c->root >> (4 * i)) & 15u);
-            if (in) ks.push_back(k);
+            if (sub_in_region(k, c->root, 8)) ks.push_back(k);
         }
     *n = ks.size();
     if (!keys) return GM_OK;
@@ -1465,78 +1465,7 @@ static int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap,
     }
     std::sort(ks.begin(), ks.end());
     std::copy(ks.begin(), ks.end(), keys);
-    return dist_box_query(c, keys, recs, ks.size());
-}
-
-// Digest of the boxes this context's ranks computed: the whole region over all virtual ranks,
-// this rank's part in a multi-process solve (the parts sum to the whole).
-static int dist_box_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    DistBox *d = c->dist_box;
-    GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, c->stream));
-    for (auto &R : d->ranks)
-        if (R.table) box_launch_digest(R.table, R.d_boxes, R.boxes.size(), c->root, d->d_acc, c->stream);
-    GM_HIP(hipGetLastError());
-    unsigned long long h[2];
-    GM_HIP(hipMemcpyAsync(h, d->d_acc, 16, hipMemcpyDeviceToHost, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    *digest = h[0];
-    *n = h[1];
-    return GM_OK;
-}
-
-// census of the same boxes: every virtual rank's, or this process's own
-static int dist_box_histogram(Ctx *c, Hist *out) {
-    DistBox *d = c->dist_box;
-    CodeBins b;
-    GM_TRY(code_bins_begin(c, &b));
-    int rc = GM_OK;
-    for (auto &R : d->ranks)
-        if (R.table && rc == GM_OK) rc = code_bins_launch<1>(c, &b, R.table, R.d_boxes, R.boxes.size(), 12, 8);
-    const int rc2 = code_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
-}
-
-// gm_select over the same boxes (select_common.hpp)
-static int dist_box_select(Ctx *c, const SelectDev &s) {
-    DistBox *d = c->dist_box;
-    for (auto &R : d->ranks)
-        if (R.table) GM_TRY(byte_select_launch<1>(c, s, R.table, R.d_boxes, R.boxes.size(), 12, 8));
-    return GM_OK;
-}
-
-// gm_moves: every code read from its box's holder, as box_launch_query reads it (moves_common.hpp)
-static int dist_box_moves(Ctx *c, const MovesReq &r) {
-    DistBox *d = c->dist_box;
-    return moves_run(c, r, [&](const MovesDev &mv) { return byte_moves_launch<1>(c, mv, d->d_tables, d->d_owner, 0, 8); });
-}
-
-// gm_verify over every virtual rank's own boxes; each code, a position's own and its children's,
-// is read from its box's holder as box_launch_query reads it (d_owner, d_tables)
-static int dist_box_verify(Ctx *c, const VerifyDev &v) {
-    DistBox *d = c->dist_box;
-    for (auto &R : d->ranks)
-        if (R.table) GM_TRY(byte_verify_launch<1>(c, v, d->d_tables, d->d_owner, R.d_boxes, R.boxes.size(), 12, 0, 8));
-    return GM_OK;
-}
-
-static int dist_box_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    DistBox *d = c->dist_box;
-    bool in = words[0] < (1ull << 32);
-    for (int j = 0; j < 8 && in; j++) in = ((words[0] >> (4 * j)) & 15u) <= ((c->root >> (4 * j)) & 15u);
-    const uint32_t idx = in ? box_index_of_key((uint32_t)words[0]) : 0u;
-    uint8_t own = 0xFF;
-    const uint8_t *tab = nullptr;
-    if (in) {
-        GM_HIP(hipMemcpy(&own, d->d_owner + (idx >> 12), 1, hipMemcpyDeviceToHost));
-        if (own != 0xFF) GM_HIP(hipMemcpy(&tab, d->d_tables + own, sizeof tab, hipMemcpyDeviceToHost));
-    }
-    if (!tab) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-    const int code = code_of_record(rec);
-    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
-    const uint8_t b = (uint8_t)code;
-    GM_HIP(hipMemcpyAsync((uint8_t *)tab + idx, &b, 1, hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    return GM_OK;
+    return byte_query(c, keys, recs, ks.size());
 }
 
 static int dist_box_table(Ctx *c, void **p, uint64_t *bytes) {
@@ -1608,7 +1537,7 @@ static void dist_box_free(Ctx *c) {
         if (q) (void)hipFree(q);
     for (int a = 0; a < 3; a++)
         if (d->own_comm[a] && d->comm[a]) (void)ncclCommDestroy(d->comm[a]);
-    for (void *q : {(void *)d->d_acc, (void *)d->d_root, (void *)d->d_owner, (void *)d->d_tables, (void *)d->d_seq,
+    for (void *q : {(void *)d->d_root, (void *)d->d_owner, (void *)d->d_tables, (void *)d->d_seq,
                     (void *)d->d_scratch})
         if (q) (void)hipFree(q);
     delete d;
@@ -1703,7 +1632,7 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
 }
 
 GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
-                 dist_box_query, dist_box_digest, dist_box_histogram, dist_box_select, dist_box_table, dist_box_free,
-                 dist_box_verify, dist_box_poke, nullptr, dist_box_moves)
+                 byte_query, byte_digest, byte_histogram, byte_select, dist_box_table, dist_box_free,
+                 byte_verify, byte_poke, nullptr, byte_moves, dist_box_bytes)
 
 }  // namespace gm

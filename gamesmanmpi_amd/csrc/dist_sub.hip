@@ -59,11 +59,7 @@
 // streams, a receive being a device copy from the sender's ring slot after the
 // sender's pack event; a host-side scheduler interleaves the lists so that every
 // cross-rank wait is enqueued after the record it waits for.
-#include "gm_internal.hpp"
-#include "hist_common.hpp"
-#include "verify_common.hpp"
-#include "moves_common.hpp"
-#include "select_common.hpp"
+#include "byte_tables.hpp"
 
 #include <mutex>
 
@@ -117,8 +113,9 @@ struct DistSub {
     std::vector<SubRank> ranks;
     std::vector<int> lo, hi;            // per batch: tier range of X_j (empty if lo > hi)
     uint8_t *zero = nullptr;
-    unsigned long long *d_acc = nullptr;
     uint32_t *d_root = nullptr;
+    uint8_t *d_owner = nullptr;         // per high part: the place in `ranks` of its owner (0xFF: not this context's)
+    const uint8_t **d_tables = nullptr; // the ranks' tables, in the order of `ranks`
     hipEvent_t ev_fork = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     ncclComm_t comm[MAX_AXES] = {};     // comm[0] = the context's; the others split from it
     bool own_comm[MAX_AXES] = {};
@@ -203,33 +200,6 @@ __global__ void block_copy_kernel(const uint8_t *__restrict__ src, const uint32_
             if (pack) dst[stg + c] = src[blk + c];
             else dst[blk + c] = src[stg + c];
         }
-    }
-}
-
-// digest over a list of whole blocks, restricted to the root's box
-__global__ void block_digest_kernel(const uint8_t *__restrict__ table, const uint32_t *__restrict__ list,
-                                    uint64_t nblocks, int low, int heaps, uint64_t root,
-                                    unsigned long long *acc) {
-    const uint64_t bsz = 1ull << (4 * low);
-    uint64_t s = 0, k = 0;
-    for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        const uint64_t base = (uint64_t)list[b] << (4 * low);
-        for (uint64_t i = threadIdx.x; i < bsz; i += blockDim.x) {
-            uint64_t key = base + i;
-            bool in = true;
-            for (int j = 0; j < heaps; j++) in &= ((key >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-            if (!in) continue;
-            s += digest_term(key, record_of_code(table[key]));
-            k++;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o);
-        k += __shfl_xor(k, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(acc, (unsigned long long)s);
-        atomicAdd(acc + 1, (unsigned long long)k);
     }
 }
 
@@ -516,7 +486,6 @@ static int prepare(Ctx *c, DistSub *d, int G, bool loopback) {
     size_t zb = std::max<size_t>(16, 1ull << (4 * d->low));
     GM_HIP(hipMalloc(&d->zero, zb));
     GM_HIP(hipMemset(d->zero, 0, zb));
-    GM_HIP(hipMalloc(&d->d_acc, 16));
     GM_HIP(hipMalloc(&d->d_root, 4));
     GM_HIP(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
     GM_HIP(hipEventCreate(&d->ev_t0));
@@ -555,6 +524,19 @@ static int prepare(Ctx *c, DistSub *d, int G, bool loopback) {
         GM_TRY(upload_xdst(d, R));
         build_ops(d, R);
     }
+    // the read side's table array and owner map (dist_sub_bytes)
+    std::vector<const uint8_t *> tabs;
+    for (auto &R : d->ranks) tabs.push_back(R.table);
+    std::vector<uint8_t> own(1ull << (4 * d->high), 0xFF);
+    for (uint64_t H = 0; H < own.size(); H++) {
+        const int r = owner_of(d, H);
+        for (size_t i = 0; i < d->ranks.size(); i++)
+            if (d->ranks[i].rank == r) own[H] = (uint8_t)i;
+    }
+    GM_HIP(hipMalloc(&d->d_tables, tabs.size() * sizeof(uint8_t *)));
+    GM_HIP(hipMemcpy(d->d_tables, tabs.data(), tabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice));
+    GM_HIP(hipMalloc(&d->d_owner, own.size()));
+    GM_HIP(hipMemcpy(d->d_owner, own.data(), own.size(), hipMemcpyHostToDevice));
     return GM_OK;
 }
 
@@ -735,49 +717,16 @@ static int dist_sub_solve(Ctx *c, uint64_t root) {
 }
 
 // ---------------------------------------------------------------- results
-static bool in_box(uint64_t k, uint64_t root, int heaps) {
-    for (int i = 0; i < heaps; i++)
-        if (((k >> (4 * i)) & 15u) > ((root >> (4 * i)) & 15u)) return false;
-    return true;
-}
-
-static int dist_sub_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+// The read side (byte_tables.hpp): slot = key in every rank's table; a rank's units are the
+// blocks it owns, 16^low contiguous bytes each, and every code is read from the table of its
+// block's owner (d_owner, indexed by the key's high part).
+static void dist_sub_bytes(Ctx *c, ByteTables *t) {
     DistSub *d = c->dist_sub;
-    hipStream_t H = c->stream;
-    GM_HIP(hipMemsetAsync(d->d_acc, 0, 16, H));
-    for (auto &R : d->ranks) {
-        uint32_t nb = R.off.back();
-        if (nb) hipLaunchKernelGGL(block_digest_kernel, dim3(std::min<uint32_t>(nb, 8192)), dim3(256), 0, H, R.table,
-                                   R.dlist, (uint64_t)nb, d->low, d->heaps, c->root, d->d_acc);
-    }
-    unsigned long long h[2];
-    GM_HIP(hipMemcpyAsync(h, d->d_acc, 16, hipMemcpyDeviceToHost, H));
-    GM_HIP(hipStreamSynchronize(H));
-    *digest = h[0];
-    *n = h[1];
-    return GM_OK;
-}
-
-// census of the blocks the ranks own: a block is 16^low contiguous bytes of its rank's table
-static int dist_sub_histogram(Ctx *c, Hist *out) {
-    DistSub *d = c->dist_sub;
-    CodeBins b;
-    GM_TRY(code_bins_begin(c, &b));
-    int rc = GM_OK;
-    for (auto &R : d->ranks) {
-        const uint32_t nb = R.off.back();
-        if (nb && rc == GM_OK) rc = code_bins_launch<0>(c, &b, R.table, R.dlist, nb, 4 * d->low, d->heaps);
-    }
-    const int rc2 = code_bins_end(c, &b, out);
-    return rc != GM_OK ? rc : rc2;
-}
-
-// gm_select over the same blocks (select_common.hpp)
-static int dist_sub_select(Ctx *c, const SelectDev &s) {
-    DistSub *d = c->dist_sub;
-    for (auto &R : d->ranks)
-        if (R.off.back()) GM_TRY(byte_select_launch<0>(c, s, R.table, R.dlist, R.off.back(), 4 * d->low, d->heaps));
-    return GM_OK;
+    t->heaps = d->heaps;
+    t->ushift = t->oshift = 4 * d->low;
+    t->d_tables = d->d_tables;
+    t->d_owner = d->d_owner;
+    for (auto &R : d->ranks) t->parts.push_back({R.table, R.dlist, R.off.back()});
 }
 
 static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
@@ -800,7 +749,7 @@ static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap,
         for (uint32_t b = 0; b < nb; b++)
             for (uint64_t i = 0; i < bsz; i++) {
                 uint64_t key = ((uint64_t)hl[b] << (4 * d->low)) + i;
-                if (!in_box(key, c->root, d->heaps)) continue;
+                if (!sub_in_region(key, c->root, d->heaps)) continue;
                 total++;
                 if (keys) out.emplace_back(key, record_of_code(hs[(uint64_t)b * bsz + i]));
             }
@@ -810,87 +759,6 @@ static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap,
     if (cap < total) { set_error("export buffer too small"); return GM_E_CAP; }
     std::sort(out.begin(), out.end());
     for (uint64_t i = 0; i < total; i++) { keys[i] = out[i].first; recs[i] = out[i].second; }
-    return GM_OK;
-}
-
-static int dist_sub_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    DistSub *d = c->dist_sub;
-    for (uint64_t i = 0; i < n; i++) {
-        recs[i] = REC_UNSOLVED;
-        if (keys[i] >> (4 * d->heaps)) continue;
-        bool in = true;   // outside the root's region: unsolved (include/gmsolve.h gm_query)
-        for (int j = 0; j < d->heaps && in; j++) in = ((keys[i] >> (4 * j)) & 15u) <= ((c->root >> (4 * j)) & 15u);
-        if (!in) continue;
-        int own = owner_of(d, keys[i] >> (4 * d->low));
-        for (auto &R : d->ranks)
-            if (R.rank == own) {
-                uint8_t s;
-                GM_HIP(hipMemcpy(&s, R.table + keys[i], 1, hipMemcpyDeviceToHost));
-                recs[i] = record_of_code(s);
-            }
-    }
-    return GM_OK;
-}
-
-// the position in d->ranks of the rank that owns high part H (0xFF: not one of this context's)
-static uint8_t holder_of(const DistSub *d, uint64_t H) {
-    const int own = owner_of(d, H);
-    for (size_t i = 0; i < d->ranks.size(); i++)
-        if (d->ranks[i].rank == own) return (uint8_t)i;
-    return 0xFF;
-}
-
-// gm_verify over the blocks the virtual ranks own (verify_common.hpp): a block is 16^low
-// contiguous bytes of its owner's table, and every code -- a position's own and its
-// children's -- is read from its owner's table, as dist_sub_query reads it
-static int dist_sub_verify(Ctx *c, const VerifyDev &v) {
-    DistSub *d = c->dist_sub;
-    std::vector<uint8_t> own(1ull << (4 * d->high));
-    for (uint64_t H = 0; H < own.size(); H++) own[H] = holder_of(d, H);
-    std::vector<const uint8_t *> tabs;
-    for (auto &R : d->ranks) tabs.push_back(R.table);
-    DevBuf<uint8_t> d_own;
-    DevBuf<const uint8_t *> d_tabs;
-    GM_TRY(d_own.alloc(own.size()));
-    GM_TRY(d_tabs.alloc(tabs.size()));
-    GM_HIP(hipMemcpyAsync(d_own, own.data(), own.size(), hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipMemcpyAsync(d_tabs, tabs.data(), tabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    for (auto &R : d->ranks)
-        GM_TRY(byte_verify_launch<0>(c, v, d_tabs.p, d_own.p, R.dlist, R.off.back(), 4 * d->low, 4 * d->low, d->heaps));
-    GM_HIP(hipStreamSynchronize(c->stream));   // the temporaries leave scope
-    return GM_OK;
-}
-
-// gm_moves: every code read from the table of its block's owner, as dist_sub_verify reads it
-// (moves_common.hpp)
-static int dist_sub_moves(Ctx *c, const MovesReq &r) {
-    DistSub *d = c->dist_sub;
-    std::vector<uint8_t> own(1ull << (4 * d->high));
-    for (uint64_t H = 0; H < own.size(); H++) own[H] = holder_of(d, H);
-    std::vector<const uint8_t *> tabs;
-    for (auto &R : d->ranks) tabs.push_back(R.table);
-    DevBuf<uint8_t> d_own;
-    DevBuf<const uint8_t *> d_tabs;
-    GM_TRY(d_own.alloc(own.size()));
-    GM_TRY(d_tabs.alloc(tabs.size()));
-    GM_HIP(hipMemcpyAsync(d_own, own.data(), own.size(), hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipMemcpyAsync(d_tabs, tabs.data(), tabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-    GM_HIP(hipStreamSynchronize(c->stream));
-    return moves_run(c, r, [&](const MovesDev &mv) {
-        return byte_moves_launch<0>(c, mv, d_tabs.p, d_own.p, 4 * d->low, d->heaps);
-    });
-}
-
-static int dist_sub_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    DistSub *d = c->dist_sub;
-    const uint64_t k = words[0];
-    const bool in = !(k >> (4 * d->heaps)) && in_box(k, c->root, d->heaps);
-    const uint8_t h = in ? holder_of(d, k >> (4 * d->low)) : 0xFF;
-    if (h == 0xFF) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-    const int code = code_of_record(rec);
-    if (code < 0) { set_error("gm_poke: the 1-byte codes hold WIN / LOSS with remoteness <= 126"); return GM_E_ARG; }
-    const uint8_t b = (uint8_t)code;
-    GM_HIP(hipMemcpy(d->ranks[h].table + k, &b, 1, hipMemcpyHostToDevice));
     return GM_OK;
 }
 
@@ -919,8 +787,9 @@ static void dist_sub_free(Ctx *c) {
     for (int a = 0; a < MAX_AXES; a++)
         if (d->own_comm[a] && d->comm[a]) (void)ncclCommDestroy(d->comm[a]);
     if (d->zero) (void)hipFree(d->zero);
-    if (d->d_acc) (void)hipFree(d->d_acc);
     if (d->d_root) (void)hipFree(d->d_root);
+    if (d->d_owner) (void)hipFree(d->d_owner);
+    if (d->d_tables) (void)hipFree(d->d_tables);
     delete d;
     c->dist_sub = nullptr;
 }
@@ -1006,7 +875,7 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
 }
 
 GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
-                 dist_sub_query, dist_sub_digest, dist_sub_histogram, dist_sub_select, nullptr, dist_sub_free,
-                 dist_sub_verify, dist_sub_poke, nullptr, dist_sub_moves)
+                 byte_query, byte_digest, byte_histogram, byte_select, nullptr, dist_sub_free,
+                 byte_verify, byte_poke, nullptr, byte_moves, dist_sub_bytes)
 
 }  // namespace gm

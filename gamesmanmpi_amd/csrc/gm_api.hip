@@ -796,15 +796,17 @@ int gm_import(gm_ctx *h, const uint64_t *root_words, const uint64_t *key_words, 
     c->stats.solve_ms = now_ms() - t0;
     c->stats.engine = e->id;
     // the stored record of the root, 0xFFFF when the table does not hold it (gm_verify: root_ok = 0)
+    // (read as every other read is, through solved_by: the byte-table readers take their view from it)
     uint16_t rr = REC_UNSOLVED;
+    c->solved_by = e;
     const int rq = c->wide ? dist_sparse_query_wide(c, &c->root_wide, &rr, 1) : e->query(c, &c->root, &rr, 1);
     if (rq != GM_OK) {
+        c->solved_by = nullptr;
         e->free_(c);
         return rq;
     }
     c->root_record = rr;
     c->solved = true;
-    c->solved_by = e;
     if (n_positions) *n_positions = c->n_positions;
     if (root_record) *root_record = c->root_record;
     return GM_OK;

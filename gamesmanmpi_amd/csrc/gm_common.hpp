@@ -92,6 +92,15 @@ GM_HD uint16_t record_of_code(uint8_t b) {
     return (uint16_t)(b - 1u);                                   // WIN
 }
 
+// The region of a subtraction solve from `root`: a move lowers one heap, so the positions
+// reachable from the root are the keys of `heaps` nibbles with every nibble <= the root's.
+GM_HD bool sub_in_region(uint64_t key, uint64_t root, int heaps) {
+    if (heaps < 16 && (key >> (4 * heaps))) return false;
+    bool in = true;
+    for (int j = 0; j < heaps; j++) in &= ((key >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
+    return in;
+}
+
 GM_HD uint64_t mix64(uint64_t x) {
     x ^= x >> 33;
     x *= 0xff51afd7ed558ccdull;

@@ -65,6 +65,7 @@ struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
 struct VerifyDev;   // verify_common.hpp: the device accumulator of gm_verify
 struct SelectDev;   // select_common.hpp: the filter and the device accumulator of gm_select
 struct MovesReq;    // moves_common.hpp: the keys and the output arrays of gm_moves
+struct ByteTables;  // byte_tables.hpp: where a byte-table SUBTRACT engine keeps its 1-byte codes
 struct Engine;
 
 struct Ctx {
@@ -169,6 +170,10 @@ struct Engine {
     // gm_moves: every key's record, children (the plugin's gen_moves order), their records and
     // the mover's choice into the request's arrays (moves_common.hpp)
     int (*moves)(Ctx *c, const MovesReq &r);
+    // the four byte-table SUBTRACT engines: the one description of their tables that the shared
+    // readers of byte_tables.hpp (the byte_* entries of their records) work from, reached through
+    // Ctx::solved_by.  null: another engine
+    void (*bytes)(Ctx *c, ByteTables *t);
 };
 // A record is host data, defined in the host pass only: the device pass of a translation unit
 // would emit a const record too, with references to the host functions it names.
@@ -204,13 +209,9 @@ struct BxSplitFlowDesc {
 void box_launch_tier_split(uint32_t grid, uint8_t *table, const uint32_t *boxes, const uint32_t *fills,
                            const uint32_t *srcs, const uint32_t *dsts, uint8_t *msg, uint8_t *const *peers,
                            uint32_t nbox, bool fill, hipStream_t s);
-void box_launch_digest(const uint8_t *table, const uint32_t *boxes, uint64_t nbox, uint64_t root,
-                       unsigned long long *acc, hipStream_t s);
-void box_launch_query(const uint8_t *const *tables, const uint8_t *owner, uint64_t root, const uint64_t *keys,
-                      uint16_t *out, uint64_t n, hipStream_t s);
 void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc);
 void box_region_keys(uint64_t root, uint64_t *keys, uint64_t n);
-constexpr uint64_t BOX_QUERY_CHUNK = 1ull << 26;   // keys on the device at a time in a box engine query
+constexpr uint64_t BOX_QUERY_CHUNK = 1ull << 26;   // keys on the device at a time in a byte-table query (byte_tables.hpp)
 // the split box engine's per-rank figures (gm_rank_stats, gm_rank_op_ms) and its plan (gm_box_plan)
 int dist_box_rank_stats(Ctx *c, double *kernel_ms, uint64_t *boxes, uint64_t *recv_bytes, int cap, int *n);
 int dist_box_op_ms(Ctx *c, int rank, double *ms, int cap, int *n);

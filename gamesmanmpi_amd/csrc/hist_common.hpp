@@ -1,6 +1,7 @@
 // hist_common.hpp -- the census of a solved table by value and remoteness (gm_histogram):
-// the host-side accumulator every engine's *_histogram fills, the byte-table kernel of the
-// dense SUBTRACT engines and the bin helpers of the u16-score tables (sparse tiers, graph).
+// the host-side accumulator every engine's histogram entry fills, the byte-table kernel of the
+// dense SUBTRACT engines (its host side: byte_histogram, byte_tables.hpp) and the bin helpers of
+// the u16-score tables (sparse tiers, graph).
 //
 // Byte tables (gm_common.hpp 1-byte codes).  The kernel counts the 256 codes; the host maps
 // code -> (value, remoteness) with record_of_code.  A lane loads 16 bytes (one CHUNK) at a

@@ -1,7 +1,7 @@
 // moves_common.hpp -- every move of a batch of positions valued on the device (gm_moves): the
-// request an engine's *_moves answers, the chunked two-pass driver the device engines share,
+// request an engine's moves entry answers, the chunked two-pass driver the device engines share,
 // the order and rank helpers of the kernels, and the byte-table kernel of the dense SUBTRACT
-// engines.  The tier-table kernel is res_moves_kernel (sparse_tables.hpp), the graph engine's
+// engines (its host side: byte_moves, byte_tables.hpp).  The tier-table kernel is res_moves_kernel (sparse_tables.hpp), the graph engine's
 // graph_moves_kernel (graph.hip).
 //
 // It is gm_verify's edge pass (verify_common.hpp: parent -> children -> records) driven by the
@@ -184,7 +184,7 @@ namespace {
 // Byte tables of the subtraction game, in byte_verify_kernel's two layouts (verify_common.hpp:
 // slot = key, BOX = 0; box-indexed, BOX = 1) and read where gm_query reads them
 // (tables[owner[unit]]).  A key outside the root's region -- a nibble above the root's, or past
-// the table -- has no record, as in sub_query_kernel / box_query_kernel.  The children are
+// the table -- has no record, as in byte_query_kernel (byte_tables.hpp).  The children are
 // DescSub::visit's, heap by heap, take 1 then take 2; a child of a key of the region is in the
 // region.  As in byte_verify_kernel all 16 one-byte loads are issued before the first is used
 // (a pair that is no move loads the position's own byte and is ignored), and the 16 codes stay
@@ -192,14 +192,13 @@ namespace {
 template <int BOX>
 __global__ __launch_bounds__(256) void byte_moves_kernel(const uint8_t *const *__restrict__ tables,
                                                          const uint8_t *__restrict__ owner, int oshift, int heaps,
-                                                         uint64_t slots, uint32_t root, MovesDev mv) {
+                                                         uint32_t root, MovesDev mv) {
     if (BOX) heaps = 8;   // the box layout is the 8-heap game's: a constant for the unrolled loops
     for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < mv.m; i += (uint64_t)gridDim.x * 256ull) {
         const uint64_t k64 = ((const uint64_t *)mv.keys)[i];
         const uint32_t key = (uint32_t)k64;
         if (!mv.fill) {
-            bool in = k64 < slots;
-            for (int j = 0; j < heaps; j++) in &= ((key >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
+            const bool in = sub_in_region(k64, root, heaps);
             uint16_t rec = REC_UNSOLVED;
             uint32_t cnt = 0;
             if (in) {
@@ -252,14 +251,13 @@ __global__ __launch_bounds__(256) void byte_moves_kernel(const uint8_t *const *_
 
 }  // namespace
 
-// one pass over a chunk, for the four byte-table engines
+// one pass over a chunk, for the four byte-table engines (byte_moves, byte_tables.hpp)
 template <int BOX>
 inline int byte_moves_launch(Ctx *c, const MovesDev &mv, const uint8_t *const *tables, const uint8_t *owner, int oshift,
                              int heaps) {
     if (!mv.m) return GM_OK;
-    const uint64_t slots = 1ull << (4 * heaps);
     hipLaunchKernelGGL(byte_moves_kernel<BOX>, dim3(grid_counted(mv.m)), dim3(256), 0, c->stream, tables, owner, oshift,
-                       heaps, slots, (uint32_t)c->root, mv);
+                       heaps, (uint32_t)c->root, mv);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }

@@ -1,6 +1,7 @@
 // select_common.hpp -- the positions of a solved table with a wanted value and a remoteness in
-// range (gm_select): the device accumulator every engine's *_select appends to, the predicate,
-// the wave-aggregated append and the byte-table kernel of the dense SUBTRACT engines.
+// range (gm_select): the device accumulator every engine's select entry appends to, the predicate,
+// the wave-aggregated append and the byte-table kernel of the dense SUBTRACT engines (its host
+// side: byte_select, byte_tables.hpp).
 //
 // A selection is the census pass (hist_common.hpp) with a predicate and a compacted output.
 // Accumulator: u64 words [0] matches, [1] the list's cursor; the list is `cap` keys and `cap`

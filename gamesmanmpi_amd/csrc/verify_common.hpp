@@ -1,6 +1,7 @@
 // verify_common.hpp -- the consistency check of a solved table against the game rules
-// (gm_verify): the device accumulator every engine's *_verify adds to, the one function that
-// names a position's class, and the byte-table kernel of the dense SUBTRACT engines.
+// (gm_verify): the device accumulator every engine's verify entry adds to, the one function that
+// names a position's class, and the byte-table kernel of the dense SUBTRACT engines (its host
+// side, and gm_poke's: byte_verify and byte_poke, byte_tables.hpp).
 //
 // A table of an acyclic game is the solution iff the root is in it, every primitive position
 // stored carries (primitive value, 0), and every interior position stored has all its children
@@ -93,9 +94,7 @@ __global__ __launch_bounds__(256) void byte_verify_kernel(const uint8_t *const *
         const uint64_t unit = x >> ushift;
         const uint32_t idx = (uint32_t)((((uint64_t)(list ? list[unit] : (uint32_t)unit)) << ushift) | (x & within));
         const uint32_t key = BOX ? box_key_of_index(idx) : idx;
-        bool in = true;
-        for (int j = 0; j < heaps; j++) in &= ((key >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
-        if (!in) continue;
+        if (!sub_in_region(key, root, heaps)) continue;
         const uint32_t stored = score_of_code(byte_code_at<BOX>(tables, owner, oshift, idx));
         const int prim = d.primitive(key);
         uint32_t best = 0;
