@@ -627,7 +627,7 @@ template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI =
 __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *p0, uint8_t *p1, uint8_t *p2,
                                          const BxGroup &G, const uint32_t *s, uint32_t lane, uint32_t i0 = 0) {
     constexpr bool SHARD = SHARD_ && !(GM_BOX_EXP & 32);
-    static_assert(!(MIRROR && SHARD_), "the mirrored store is the one-GPU tier launches'");
+    static_assert(!(MIRROR && SHARD_), "the mirrored store is the one-GPU launches'");
     __amdgpu_buffer_rsrc_t w[2];
     uint32_t tw[2][3] = {{0, 0, 0}, {0, 0, 0}};   // MIRROR: the twins of box k (bx_twin_rsrc)
 #pragma unroll
@@ -1065,6 +1065,8 @@ __global__ __launch_bounds__(256) void box_tier4_kernel(uint8_t *__restrict__ ta
 #endif
 // the hand-off needs the producer's rows written through to the coherent level before its flag
 static_assert(GM_BOX_STORE_CPOL & 16, "box_flow_kernel publishes flags after sc1 stores: keep GM_BOX_STORE_CPOL sc1");
+static_assert(GM_BOX_MIRROR_STORE_CPOL & 16,
+              "box_flow_kernel RANGE publishes the twins' flags after their stores: keep GM_BOX_MIRROR_STORE_CPOL sc1");
 struct BxFlow {
     const uint32_t *groups;   // queue q: groups[qbase[q] + j], j < qlen[q]: box-list index | second box << 31
     uint32_t qbase[8], qlen[8];
@@ -1140,11 +1142,26 @@ __device__ unsigned long long bx_ftrace[BX_FT_WORDS * BX_FT_GROUPS];
     } while (0)
 #endif
 
-template <bool SHARD>
+// RANGE (the hybrid schedule's head and tail launches): the queues hold
+// the groups of a range of box-tiers of the compute list (box_common.hpp), so box[k] keeps its
+// mirror flags and a flagged box is stored two or four times, as by the tier launches
+// (bx_store MIRROR).  Every box stored gets its flag, the twins included: a parent may wait on
+// a box that no group computed.  A record with BX_FLOW_NOWAIT is of the range's first tier:
+// its children were stored by an earlier launch of the same stream, and it does not wait.
+// (Its child rows are still read sc1, like every group's: a load policy chosen per group would
+// put the 48 loads of bx_issue into the kernel twice.)
+// The no-deadlock argument above holds for these lists as it stands: a twin's flag is set by
+// the group dequeued for its leader, and the leader is in the twin's own tier (a mirror
+// exchanges two coordinates and keeps their sum), so the group of the lowest tier still has
+// every child's flag coming from groups of the tier before, all of them finished or, in the
+// first tier of the range, stored by an earlier launch.
+constexpr uint32_t BX_FLOW_NOWAIT = 0x40000000u;   // bit 30 of a queue record (RANGE)
+template <bool SHARD, bool RANGE = false>
 __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_flow_kernel(uint8_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ boxes,
                                                                      const uint32_t *__restrict__ fills,
                                                                      const uint32_t *__restrict__ srcs, BxFlow F) {
+    static_assert(!(SHARD && RANGE), "the tier-range launches are the one-GPU solve's");
     __shared__ __attribute__((aligned(16))) uint32_t lds[BX_LDS];
     uint32_t *s = lds + BX_PAD;
     const uint32_t lane = threadIdx.x, q = blockIdx.x & 7u, qn = F.qlen[q];
@@ -1163,8 +1180,11 @@ __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_flow_kernel(uint8_t *__r
         unsigned long long ft[5];
         BX_RT(ft[0]);
 #endif
-        const BxGroup G = bx_group_rec<SHARD>(boxes, fills, srcs, gq[j], lane);
-        const uint32_t src = lane < 16u ? bx_child_src<SHARD>(G, lane >> 3, lane & 7u) : ~0u;
+        const uint32_t rec = gq[j];
+        const BxGroup G = bx_group_rec<SHARD>(boxes, fills, srcs, RANGE ? rec & ~BX_FLOW_NOWAIT : rec, lane);
+        uint32_t src = lane < 16u ? bx_child_src<SHARD>(G, lane >> 3, lane & 7u) : ~0u;
+        if constexpr (RANGE)   // (the child of a list entry: its mirror flags off; uniform: no waits)
+            src = ((rec & BX_FLOW_NOWAIT) || src == ~0u) ? ~0u : src & BX_BOX_MASK;
         const uint32_t seen = bx_flag_src_load(F, src);
         if (!(F.dev & 1u) && !bx_wait(F, src, seen, lane, ep)) return;
 #if GM_BOX_FLOW_TRACE
@@ -1186,11 +1206,23 @@ __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_flow_kernel(uint8_t *__r
 #if GM_BOX_FLOW_TRACE
         BX_RT(ft[3]);
 #endif
-        bx_store<false>(table, nullptr, nullptr, nullptr, nullptr, G, s, ln);
+        bx_store<false, false, GM_BOX_STORE_CPOL, 4, RANGE>(table, nullptr, nullptr, nullptr, nullptr, G, s, ln);
         BX_LDS_ORDER();
         // publish: the wave's sc1 stores done, then one lane stores each box's flag sc1
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
+        if constexpr (RANGE) {
+            // lane 4 k + v: box k itself (v = 0) or its twin under the 6/7 mirror (v & 1), the
+            // 4/5 mirror (v & 2) or both -- the boxes bx_store wrote, by the entry's flags
+            if (lane < 8u) {
+                const uint32_t e = (lane >> 2) ? G.box[1] : G.box[0], v = lane & 3u;
+                uint32_t b = e & BX_BOX_MASK;
+                if (v & 1u) b = bx_swap67(b);
+                if (v & 2u) b = bx_swap45(b);
+                const bool on = ((lane >> 2) ? G.valid[1] : G.valid[0]) && (!(v & 1u) || (e & BX_MIRROR_FLAG)) &&
+                                (!(v & 2u) || (e & BX_MIRROR45_FLAG));
+                if (on) __hip_atomic_store(&F.flag[b], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        } else if (lane == 0) {
             __hip_atomic_store(&F.flag[G.box[0]], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (G.valid[1]) __hip_atomic_store(&F.flag[G.box[1]], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1417,6 +1449,17 @@ int box_split_flow_resident(int device) {
                     box_resident((const void *)box_split_flow_kernel<false>, device, 0));
 }
 
+// The hybrid schedule's default tier range (GM_BOX_HYBRID, box_hybrid_wanted); 0, 40 = off.
+// Measured: the thin tiers alone, (10, 30), gain nothing over tier launches;
+// the ramp tiers pay, up to (14, 26); from (16, 24) on the thick tiers' sc1 child loads lose.
+#ifndef GM_BOX_HYBRID_LO
+#define GM_BOX_HYBRID_LO 14
+#endif
+#ifndef GM_BOX_HYBRID_HI
+#define GM_BOX_HYBRID_HI 26
+#endif
+constexpr int BOX_HYBRID_OFF_HI = 40;
+
 struct DenseBox {
     uint32_t root_hi = 0;
     uint8_t *table = nullptr;
@@ -1438,10 +1481,17 @@ struct DenseBox {
     bool flow = false;                // one-launch (dataflow) solve (GM_OPT_BOX_FLOW)
     int flow_grid = 0;                // the dataflow launch's grid: its resident capacity
     size_t flow_dyn = 0;              // dynamic LDS of the dataflow launch (GM_BOX_FLOW_EXTRA_LDS, tests)
-    uint32_t *d_flow = nullptr;       // [0, 9) error word at [8], [16] epoch, [64, 64 + 2^20) box flags
+    uint32_t *d_flow = nullptr;       // [0, 9) error word at [8] (hybrid: the tail's at [9]), [16] epoch, [64, 64 + 2^20) box flags
     uint32_t *d_groups = nullptr;     // the 8 group queues (BxFlow)
     uint32_t qbase[8] = {}, qlen[8] = {};
-    uint32_t *h_res = nullptr;        // pinned: [0] the root's code (low byte), [1] the dataflow error word
+    // hybrid schedule (GM_BOX_HYBRID): box-tiers [0, hyb_lo) in one dataflow launch over the compute
+    // list, [hyb_lo, hyb_hi] as tier launches, the rest in a second dataflow launch; queues,
+    // grid and error word (d_flow[8 + w]) of launch w = 0 (head), 1 (tail)
+    int hyb_lo = 0, hyb_hi = BOX_HYBRID_OFF_HI;
+    bool hyb = false;                 // some box-tier runs in a dataflow launch
+    uint32_t hqbase[2][8] = {}, hqlen[2][8] = {};
+    int hyb_grid[2] = {0, 0};
+    uint32_t *h_res = nullptr;        // pinned: [0] the root's code (low byte), [1], [2] the dataflow error words
 };
 
 // GM_BOX_FLOW (development, overrides GM_OPT_BOX_FLOW): 0 tier launches, 1 dataflow, 2 dataflow
@@ -1456,19 +1506,45 @@ static bool box_flow_wanted(const Ctx *c) {
     return c->box_flow == 1 && !c->box_flow_failed;
 }
 
+// GM_BOX_HYBRID=lo,hi (development, read at prepare): box-tiers [0, lo) run as one dataflow
+// launch over the compute list, [lo, hi] as tier launches, (hi, 40] as a second dataflow launch
+// (lo > hi: every tier in the first).  0,40 = tier launches only.  Only this engine (one GPU,
+// unsharded) has it; off with the whole-solve dataflow, with GM_BOX_FLOW set, and after a
+// dataflow solve of the context timed out.  false: the variable does not parse.
+static bool box_hybrid_wanted(const Ctx *c, int *lo, int *hi) {
+    *lo = GM_BOX_HYBRID_LO;
+    *hi = GM_BOX_HYBRID_HI;
+    if (const char *e = getenv("GM_BOX_HYBRID")) {
+        char tail = 0;
+        if (sscanf(e, "%d,%d%c", lo, hi, &tail) != 2 || *lo < 0 || *lo > 41 || *hi < 0 || *hi > 40) {
+            set_error("GM_BOX_HYBRID must be lo,hi with 0 <= lo <= 41 and 0 <= hi <= 40 (got %s)", e);
+            return false;
+        }
+    }
+    if (box_flow_wanted(c) || box_flow_env() >= 0 || c->box_flow_failed) {
+        *lo = 0;
+        *hi = BOX_HYBRID_OFF_HI;
+    }
+    return true;
+}
+
 // The tier launches' groups in 8 queues: queue x = every tier's XCD run x, tier after
 // tier.  Inside a run the groups are ordered by when their child boxes are stored: a
 // group's key is the latest normalised position (0..1 along its queue's run) of its
 // children in the tier before, and the run is sorted by key (stable: Hilbert order among
 // equals), so the first rounds of a tier take the groups whose children the first rounds
 // of the tier before made (GM_BOX_FLOW_ORDER 0: Hilbert order only).
-static void box_flow_queues(DenseBox &R, std::vector<uint32_t> &out) {
+// Hybrid schedule: `boxes` / `tier_off` are the compute list, the queues hold box-tiers [t0, t1)
+// only and are appended to `out`; an entry's mirror flags are masked where it names a box, its
+// twins (stored by its group) get its position, and the groups of tier t0 carry BX_FLOW_NOWAIT
+// (range): their children are an earlier launch's.
+static void box_flow_queues(const std::vector<uint32_t> &boxes, const std::vector<uint32_t> &tier_off, size_t t0,
+                            size_t t1, bool range, uint32_t *qbase, uint32_t *qlen, std::vector<uint32_t> &out) {
     static const int order = getenv("GM_BOX_FLOW_ORDER") ? atoi(getenv("GM_BOX_FLOW_ORDER")) : 1;
-    const std::vector<uint32_t> &boxes = R.boxes;
     std::vector<uint32_t> q[8];
     std::vector<float> when(1u << 20, 0.0f);   // per box id: normalised position of its group
-    for (size_t t = 0; t + 1 < R.tier_off.size(); t++) {
-        const uint32_t o = R.tier_off[t], nb = R.tier_off[t + 1] - o, ng = (nb + 1) / 2;
+    for (size_t t = t0; t < t1; t++) {
+        const uint32_t o = tier_off[t], nb = tier_off[t + 1] - o, ng = (nb + 1) / 2;
         const uint32_t qq = ng >> 3, r = ng & 7u;
         for (uint32_t x = 0; x < 8; x++) {
             const uint32_t g0 = x * qq + (x < r ? x : r), g1 = g0 + qq + (x < r ? 1u : 0u);
@@ -1481,26 +1557,30 @@ static void box_flow_queues(DenseBox &R, std::vector<uint32_t> &out) {
                     for (uint32_t k = 0; k < (two ? 2u : 1u); k++)
                         for (int dir = 0; dir < 8; dir++)
                             if (box_coord(boxes[i + k], dir) >= 1)
-                                key = std::max(key, when[boxes[i + k] - box_unit(dir)]);
-                run.push_back({key, i | (two ? 0x80000000u : 0u)});
+                                key = std::max(key, when[(boxes[i + k] & BX_BOX_MASK) - box_unit(dir)]);
+                run.push_back({key, i | (two ? 0x80000000u : 0u) | ((range && t == t0) ? BX_FLOW_NOWAIT : 0u)});
             }
             std::stable_sort(run.begin(), run.end(),
                              [](const std::pair<float, uint32_t> &a, const std::pair<float, uint32_t> &b) {
                                  return a.first < b.first;
                              });
             for (size_t n = 0; n < run.size(); n++) {
-                const uint32_t rec = run[n].second, i = rec & 0x7FFFFFFFu;
+                const uint32_t rec = run[n].second, i = rec & (BX_FLOW_NOWAIT - 1u);
                 const float w = (float)(n + 1) / (float)run.size();
-                when[boxes[i]] = w;
-                if (rec >> 31) when[boxes[i + 1]] = w;
+                for (uint32_t k = 0; k < (rec >> 31 ? 2u : 1u); k++) {
+                    const uint32_t e = boxes[i + k], b = e & BX_BOX_MASK;
+                    when[b] = w;
+                    if (e & BX_MIRROR_FLAG) when[bx_swap67(b)] = w;
+                    if (e & BX_MIRROR45_FLAG) when[bx_swap45(b)] = w;
+                    if ((e & BX_MIRROR_FLAG) && (e & BX_MIRROR45_FLAG)) when[bx_swap45(bx_swap67(b))] = w;
+                }
                 q[x].push_back(rec);
             }
         }
     }
-    out.clear();
     for (int x = 0; x < 8; x++) {
-        R.qbase[x] = (uint32_t)out.size();
-        R.qlen[x] = (uint32_t)q[x].size();
+        qbase[x] = (uint32_t)out.size();
+        qlen[x] = (uint32_t)q[x].size();
         out.insert(out.end(), q[x].begin(), q[x].end());
     }
 }
@@ -1560,25 +1640,39 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     GM_HIP(hipMalloc(&d->d_boxes, std::max<size_t>(1, d->boxes.size()) * 4));
     GM_HIP(hipMemcpy(d->d_boxes, d->boxes.data(), d->boxes.size() * 4, hipMemcpyHostToDevice));
     d->mirror = c->symmetry != 0;
-    {
-        std::vector<uint32_t> cb;
-        box_compute_list(d->root_hi, d->mirror, d->boxes, d->tier_off, cb, d->ctier_off);
-        GM_HIP(hipMalloc(&d->d_cboxes, std::max<size_t>(1, cb.size()) * 4));
-        GM_HIP(hipMemcpy(d->d_cboxes, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
-    }
+    std::vector<uint32_t> cb;
+    box_compute_list(d->root_hi, d->mirror, d->boxes, d->tier_off, cb, d->ctier_off);
+    GM_HIP(hipMalloc(&d->d_cboxes, std::max<size_t>(1, cb.size()) * 4));
+    GM_HIP(hipMemcpy(d->d_cboxes, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
     d->flow = box_flow_wanted(c);
-    if (d->flow) {
+    if (!box_hybrid_wanted(c, &d->hyb_lo, &d->hyb_hi)) return GM_E_ARG;
+    // the head launch's tiers [0, h0), the tail launch's [h1, nt)
+    const size_t nt = d->tier_off.size() - 1, h0 = std::min<size_t>((size_t)d->hyb_lo, nt),
+                 h1 = std::min<size_t>(std::max<size_t>((size_t)d->hyb_hi + 1, h0), nt);
+    d->hyb = h0 > 0 || h1 < nt;
+    if (d->flow || d->hyb) {
         const size_t words = 64 + (1u << 20);
         GM_HIP(hipMalloc(&d->d_flow, words * 4));
         GM_HIP(hipMemset(d->d_flow, 0, words * 4));
         std::vector<uint32_t> qs;
-        box_flow_queues(*d, qs);
+        if (d->flow) {
+            box_flow_queues(d->boxes, d->tier_off, 0, nt, false, d->qbase, d->qlen, qs);
+        } else {
+            box_flow_queues(cb, d->ctier_off, 0, h0, true, d->hqbase[0], d->hqlen[0], qs);
+            box_flow_queues(cb, d->ctier_off, h1, nt, true, d->hqbase[1], d->hqlen[1], qs);
+        }
         GM_HIP(hipMalloc(&d->d_groups, std::max<size_t>(1, qs.size()) * 4));
         GM_HIP(hipMemcpy(d->d_groups, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
         const char *xl = getenv("GM_BOX_FLOW_EXTRA_LDS");   // tests: fewer resident workgroups
         d->flow_dyn = xl ? (size_t)std::max(0, atoi(xl)) : 0;
-        d->flow_grid = box_resident((const void *)box_flow_kernel<false>, c->device, d->flow_dyn) & ~7;
+        d->flow_grid = box_resident(d->flow ? (const void *)box_flow_kernel<false> : (const void *)box_flow_kernel<false, true>,
+                                    c->device, d->flow_dyn) & ~7;
         if (d->flow_grid < 8) { set_error("box dataflow kernel: no resident workgroups"); return GM_E_HIP; }
+        // a range launch: no more workgroups than its longest queue has groups (0: no launch)
+        for (int w = 0; w < 2; w++) {
+            const uint32_t ql = *std::max_element(d->hqlen[w], d->hqlen[w] + 8);
+            d->hyb_grid[w] = (int)std::min<uint32_t>((uint32_t)d->flow_grid, 8u * ql);
+        }
     }
     if (c->adopted_dense) {
         d->table = (uint8_t *)c->adopted_dense;
@@ -1595,14 +1689,17 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     return GM_OK;
 }
 
-static int box_launch_flow(Ctx *c, DenseBox *d) {
+// The whole-solve dataflow launch (range < 0), or launch `range` (0 head, 1 tail) of the hybrid
+// schedule: its own queues and error word, the epoch the head's (the two launches' box sets
+// are disjoint, so one epoch serves both; the tail bumps it when there is no head).
+static int box_launch_flow(Ctx *c, DenseBox *d, int range = -1) {
     BxFlow F;
     F.groups = d->d_groups;
     for (int x = 0; x < 8; x++) {
-        F.qbase[x] = d->qbase[x];
-        F.qlen[x] = d->qlen[x];
+        F.qbase[x] = range < 0 ? d->qbase[x] : d->hqbase[range][x];
+        F.qlen[x] = range < 0 ? d->qlen[x] : d->hqlen[range][x];
     }
-    F.ctr = d->d_flow;
+    F.ctr = d->d_flow + (range > 0 ? 1 : 0);   // the error word is ctr[8]: the tail's next to the head's
     F.epoch = d->d_flow + 16;
     F.flag = d->d_flow + 64;
     F.dev = box_flow_env() == 2 ? 1u : 0u;
@@ -1612,17 +1709,31 @@ static int box_launch_flow(Ctx *c, DenseBox *d) {
     const double ms = tm ? atof(tm) : 200.0;
     if (!(ms > 0.0)) { set_error("GM_BOX_FLOW_TIMEOUT_MS must be > 0 (got %s)", tm); return GM_E_ARG; }
     F.timeout = (uint64_t)(ms * 100000.0);
-    GM_HIP(hipMemsetAsync(d->d_flow, 0, 9 * 4, c->stream));
-    hipLaunchKernelGGL(box_epoch_kernel, dim3(1), dim3(64), 0, c->stream, d->d_flow + 16);
-    hipLaunchKernelGGL(box_flow_kernel<false>, dim3((uint32_t)d->flow_grid), dim3(64), d->flow_dyn, c->stream, d->table,
-                       d->d_boxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
+    // The kernel uses no word of ctr but the error word, and the hybrid's two lie side by side:
+    // the first range launch of a solve resets both in one memset node and bumps the epoch
+    // (each extra node between two launches costs the solve 3-5 us).
+    const bool first = range < 1 || !d->hyb_grid[0];
+    if (range < 0) GM_HIP(hipMemsetAsync(F.ctr, 0, 9 * 4, c->stream));
+    else if (first) GM_HIP(hipMemsetAsync(d->d_flow + 8, 0, 2 * 4, c->stream));
+    if (first) hipLaunchKernelGGL(box_epoch_kernel, dim3(1), dim3(64), 0, c->stream, d->d_flow + 16);
+    if (range < 0)
+        hipLaunchKernelGGL(box_flow_kernel<false>, dim3((uint32_t)d->flow_grid), dim3(64), d->flow_dyn, c->stream,
+                           d->table, d->d_boxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
+    else
+        hipLaunchKernelGGL((box_flow_kernel<false, true>), dim3((uint32_t)d->hyb_grid[range]), dim3(64), d->flow_dyn,
+                           c->stream, d->table, d->d_cboxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
 
 static int box_launch_tiers(Ctx *c, DenseBox *d) {
     if (d->flow) return box_launch_flow(c, d);
-    for (size_t t = 0; t + 1 < d->tier_off.size(); t++) {
+    // hybrid schedule: the head's tiers, then tier launches, then the tail's, all on the one stream
+    const size_t nt = d->tier_off.size() - 1;
+    const size_t h0 = d->hyb ? std::min<size_t>((size_t)d->hyb_lo, nt) : 0;
+    const size_t h1 = d->hyb ? std::min<size_t>(std::max<size_t>((size_t)d->hyb_hi + 1, h0), nt) : nt;
+    if (d->hyb_grid[0]) GM_TRY(box_launch_flow(c, d, 0));
+    for (size_t t = h0; t < h1; t++) {
         const uint32_t nb = d->tier_off[t + 1] - d->tier_off[t];
         if (!nb) continue;
         const uint32_t ng = (nb + 1) / 2;
@@ -1644,10 +1755,12 @@ static int box_launch_tiers(Ctx *c, DenseBox *d) {
                            (const uint32_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr,
                            (uint8_t *)nullptr, cnb);
     }
+    if (d->hyb_grid[1]) GM_TRY(box_launch_flow(c, d, 1));
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
 
+// (the hybrid schedule counts as its box-tiers: gm_stats_t.kernel_launches is the tier count)
 static int box_launches(const DenseBox *d) {
     if (d->flow) return 1;
     int n = 0;
@@ -1670,7 +1783,10 @@ void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc) {
 static int dense_box_solve(Ctx *c, uint64_t root) {
     DenseBox *d = c->dbox;
     const uint32_t rh = box_index_of_key((uint32_t)root) >> 12;
+    int hlo, hhi;
+    if (!box_hybrid_wanted(c, &hlo, &hhi)) return GM_E_ARG;
     if (!d || (c->adopted_dense && d->table != c->adopted_dense) || d->root_hi != rh || d->flow != box_flow_wanted(c) ||
+        d->hyb_lo != hlo || d->hyb_hi != hhi ||
         d->mirror != (c->symmetry != 0)) {   // (the lists and the captured graph are the option's)
         dense_box_free(c);
         d = c->dbox = new DenseBox();
@@ -1707,7 +1823,7 @@ static int dense_box_solve(Ctx *c, uint64_t root) {
         if (c->timing) GM_HIP(hipEventRecord(d->ev[1], c->stream));
     }
 #if GM_BOX_FLOW_TRACE
-    if (d->flow && getenv("GM_BOX_FLOW_TRACE_OUT")) {
+    if (d->flow && getenv("GM_BOX_FLOW_TRACE_OUT")) {   // (the whole-solve launch only: qbase of d->qbase)
         uint64_t ng = 0;
         for (int x = 0; x < 8; x++) ng += d->qlen[x];
         std::vector<unsigned long long> h(BX_FT_WORDS * std::min<uint64_t>(ng, BX_FT_GROUPS));
@@ -1733,18 +1849,18 @@ static int dense_box_solve(Ctx *c, uint64_t root) {
     }
 #endif
     // the root's code and the dataflow error word in one pinned buffer: one wait per solve
-    if (!d->h_res) GM_HIP(hipHostMalloc((void **)&d->h_res, 8, hipHostMallocDefault));
-    d->h_res[0] = d->h_res[1] = 0;
+    if (!d->h_res) GM_HIP(hipHostMalloc((void **)&d->h_res, 12, hipHostMallocDefault));
+    d->h_res[0] = d->h_res[1] = d->h_res[2] = 0;
     GM_HIP(hipMemcpyAsync(d->h_res, d->table + box_index_of_key((uint32_t)root), 1, hipMemcpyDeviceToHost, c->stream));
-    if (d->flow) GM_HIP(hipMemcpyAsync(d->h_res + 1, d->d_flow + 8, 4, hipMemcpyDeviceToHost, c->stream));
+    if (d->flow || d->hyb) GM_HIP(hipMemcpyAsync(d->h_res + 1, d->d_flow + 8, 8, hipMemcpyDeviceToHost, c->stream));
     GM_HIP(hipStreamSynchronize(c->stream));
     const uint8_t rs = (uint8_t)(d->h_res[0] & 0xFFu);
-    if (d->flow && d->h_res[1]) {
+    if ((d->flow || d->hyb) && (d->h_res[1] | d->h_res[2])) {
         // A wait timed out: solve again with the tier launches.  The context keeps tier
         // launches from then on (box_flow_failed, cleared by gm_set_option GM_OPT_BOX_FLOW);
         // every solve that fell back counts in gm_stats_t.flow_fallbacks.
-        fprintf(stderr, "gmsolve: the one-launch box solve timed out waiting for a child box; "
-                        "re-solving with tier launches\n");
+        fprintf(stderr, "gmsolve: the %s box solve timed out waiting for a child box; "
+                        "re-solving with tier launches\n", d->flow ? "one-launch" : "hybrid");
         c->box_flow_failed = true;
         c->box_flow_fallbacks++;
         const int fb = c->box_flow_fallbacks;
