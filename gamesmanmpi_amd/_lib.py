@@ -40,6 +40,7 @@ BEV_DONE, BEV_PACKED = range(2)
 REC_UNSOLVED = 0xFFFF
 SEL_WIN, SEL_LOSS, SEL_TIE, SEL_DRAW = 1, 2, 4, 8   # gm_select_t.values: 1 << value code
 SEL_ANY_REM = 0x3FFF   # gm_select_t.rem_hi: no upper bound
+REACH_ALL, REACH_BEST, REACH_FIRST = 0, 1, 2   # gm_reach_t.mover / other: a side's move policy
 
 ERRORS = {
     -1: "GM_E_ARG", -2: "GM_E_GAME", -3: "GM_E_HIP", -4: "GM_E_NOMEM", -5: "GM_E_STATE",
@@ -54,7 +55,7 @@ SYMBOLS = ("gm_version", "gm_last_error", "gm_device_count", "gm_open", "gm_set_
            "gm_rank_stats", "gm_rank_op_ms", "gm_close", "gm_key_words", "gm_pack_initial_key",
            "gm_expand_host_key", "gm_solve_key", "gm_export_key", "gm_query_key", "gm_sparse_layout",
            "gm_histogram", "gm_verify", "gm_poke", "gm_draw_count", "gm_import", "gm_select",
-           "gm_moves")
+           "gm_moves", "gm_reach")
 
 
 class GMError(RuntimeError):
@@ -130,6 +131,33 @@ class Moves(ctypes.Structure):
     ]
 
 
+class Reach(ctypes.Structure):
+    """gm_reach_t (include/gmsolve.h): the two sides' policies and the ply bound."""
+    _fields_ = [
+        ("mover", ctypes.c_uint32),
+        ("other", ctypes.c_uint32),
+        ("max_plies", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class ReachOut(ctypes.Structure):
+    """gm_reach_out_t (include/gmsolve.h): the counts of one gm_reach call."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("n_mover", ctypes.c_uint64),
+        ("n_other", ctypes.c_uint64),
+        ("n_starts", ctypes.c_uint64),
+        ("edges", ctypes.c_uint64),
+        ("missing", ctypes.c_uint64),
+        ("plies", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 def moves_dtype():
     """The numpy dtype of an array of gm_moves_t."""
     import numpy as np
@@ -173,6 +201,7 @@ def lib():
         "gm_verify": (ctypes.c_int, [vp, P(Verify), vp, u64, P(u64)]),
         "gm_select": (ctypes.c_int, [vp, P(Select), vp, vp, u64, P(u64)]),
         "gm_moves": (ctypes.c_int, [vp, vp, u64, vp, vp, vp, u64, P(u64)]),
+        "gm_reach": (ctypes.c_int, [vp, P(Reach), vp, u64, P(ReachOut), vp, ctypes.c_int, vp, vp, vp, u64]),
         "gm_poke": (ctypes.c_int, [vp, vp, ctypes.c_uint16]),
         "gm_draw_count": (ctypes.c_int, [vp, P(u64)]),
         "gm_import": (ctypes.c_int, [vp, vp, vp, vp, u64, P(u64), P(ctypes.c_uint16)]),

@@ -24,7 +24,7 @@ SOURCES = ["gm_api.hip", "dense_sub.hip", "dense_box.hip", "dist_box.hip", "smal
            "dist_sparse.hip",
            "graph.hip", "graph_loopy.hip"]
 HEADERS = ["gm_common.hpp", "box_common.hpp", "games.hpp", "gm_internal.hpp", "sparse_common.hpp", "sparse_tables.hpp",
-           "hist_common.hpp", "verify_common.hpp", "select_common.hpp", "moves_common.hpp", "byte_tables.hpp", "graph_common.hpp"]
+           "hist_common.hpp", "verify_common.hpp", "select_common.hpp", "moves_common.hpp", "reach_common.hpp", "byte_tables.hpp", "graph_common.hpp"]
 
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
             "-I" + os.path.join(REPO, "include"), "-I" + CSRC]

@@ -13,6 +13,7 @@
 #include "verify_common.hpp"
 #include "select_common.hpp"
 #include "moves_common.hpp"
+#include "reach_common.hpp"
 
 #include <type_traits>
 
@@ -187,6 +188,34 @@ int byte_moves(Ctx *c, const MovesReq &r) {
         return byte_layout(t, [&](auto B) {
             return byte_moves_launch<decltype(B)::value>(c, mv, t.d_tables, t.d_owner, t.oshift, t.heaps);
         });
+    });
+}
+
+// gm_reach: one mark unit per key of the heaps' lattice in either layout; the positions that
+// can be marked are the root's region, a position has at most two moves per heap
+int byte_reach(Ctx *c, const ReachReq &q) {
+    const ByteTables t = byte_tables_of(c);
+    if (t.heaps < 1 || t.heaps > 8) { set_error("gm_reach: byte tables of %d heaps", t.heaps); return GM_E_STATE; }
+    const uint64_t units = 1ull << (4 * t.heaps);
+    uint64_t region = 1;
+    for (int j = 0; j < t.heaps; j++) region *= ((c->root >> (4 * j)) & 15u) + 1u;
+    return byte_layout(t, [&](auto B) {
+        constexpr int BOX = decltype(B)::value;
+        const ReachBytes<BOX> acc{t.d_tables, t.d_owner, t.oshift, t.heaps, (uint32_t)c->root};
+        return reach_run(
+            c, q, ReachDims{units, region, 2ull * (uint64_t)t.heaps},
+            [&](const ReachDev &r) {
+                hipLaunchKernelGGL(reach_level_kernel<ReachBytes<BOX>>, dim3(grid_counted(r.m)), dim3(256), 0, c->stream,
+                                   acc, r);
+                GM_HIP(hipGetLastError());
+                return GM_OK;
+            },
+            [&](const ReachDev &r) {
+                hipLaunchKernelGGL(byte_reach_sweep_kernel<BOX>, dim3(grid_counted(units)), dim3(256), 0, c->stream, acc,
+                                   units, r);
+                GM_HIP(hipGetLastError());
+                return GM_OK;
+            });
     });
 }
 

@@ -1958,6 +1958,6 @@ static void dense_box_free(Ctx *c) {
 
 GM_ENGINE_RECORD(dense_box_engine, GM_ENGINE_DENSE, dense_box_solve, dense_box_export,
                  byte_query, byte_digest, byte_histogram, byte_select, dense_box_table, dense_box_free,
-                 byte_verify, byte_poke, nullptr, byte_moves, dense_box_bytes)
+                 byte_verify, byte_poke, nullptr, byte_moves, dense_box_bytes, byte_reach)
 
 }  // namespace gm

@@ -1279,6 +1279,6 @@ static int dense_sub_import(Ctx *c, const void *keys_, const uint16_t *recs, uin
 
 GM_ENGINE_RECORD(dense_sub_engine, GM_ENGINE_DENSE, dense_sub_solve, dense_sub_export,
                  byte_query, byte_digest, byte_histogram, byte_select, dense_sub_table, dense_sub_free,
-                 byte_verify, byte_poke, dense_sub_import, byte_moves, dense_sub_bytes)
+                 byte_verify, byte_poke, dense_sub_import, byte_moves, dense_sub_bytes, byte_reach)
 
 }  // namespace gm

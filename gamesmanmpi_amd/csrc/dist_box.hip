@@ -1633,6 +1633,6 @@ int dist_box_plan(uint64_t root, int world, int rank, const int32_t *opts, int w
 
 GM_ENGINE_RECORD(dist_box_engine, GM_ENGINE_DIST_DENSE, dist_box_solve, dist_box_export,
                  byte_query, byte_digest, byte_histogram, byte_select, dist_box_table, dist_box_free,
-                 byte_verify, byte_poke, nullptr, byte_moves, dist_box_bytes)
+                 byte_verify, byte_poke, nullptr, byte_moves, dist_box_bytes, byte_reach)
 
 }  // namespace gm

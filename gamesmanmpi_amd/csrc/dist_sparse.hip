@@ -1356,6 +1356,12 @@ static int dist_sparse_moves(Ctx *c, const MovesReq &r) {
     });
 }
 
+static int dist_sparse_reach(Ctx *c, const ReachReq &q) {
+    return with_desc_wide(c, [&](const auto &desc) {
+        return tiers_reach(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), q);
+    });
+}
+
 static int dist_sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     if (c->wide) {
         K128 k;
@@ -1419,6 +1425,7 @@ static int dist_sparse_import(Ctx *c, const void *keys, const uint16_t *recs, ui
 
 GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
                  dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, dist_sparse_select, nullptr, dist_sparse_free,
-                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import, dist_sparse_moves)
+                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import, dist_sparse_moves, nullptr,
+                 dist_sparse_reach)
 
 }  // namespace gm

@@ -876,6 +876,6 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
 
 GM_ENGINE_RECORD(dist_sub_engine, GM_ENGINE_DIST_DENSE, dist_sub_solve, dist_sub_export,
                  byte_query, byte_digest, byte_histogram, byte_select, nullptr, dist_sub_free,
-                 byte_verify, byte_poke, nullptr, byte_moves, dist_sub_bytes)
+                 byte_verify, byte_poke, nullptr, byte_moves, dist_sub_bytes, byte_reach)
 
 }  // namespace gm

@@ -4,6 +4,7 @@
 #include "verify_common.hpp"
 #include "select_common.hpp"
 #include "moves_common.hpp"
+#include "reach_common.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -218,6 +219,134 @@ int moves_run(Ctx *c, const MovesReq &r, const std::function<int(const MovesDev 
     if (r.child_words && r.cap && base > r.cap) {
         set_error("gm_moves: the child arrays hold %llu, need %llu", (unsigned long long)r.cap, (unsigned long long)base);
         return GM_E_CAP;
+    }
+    return GM_OK;
+}
+
+// frontier entries per launch of gm_reach: GM_REACH_CHUNK (a development variable, as
+// GM_MOVES_CHUNK) lets a test cross chunk boundaries with a small table
+static uint64_t reach_chunk() {
+    const char *e = getenv("GM_REACH_CHUNK");
+    const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+    return v ? std::min<uint64_t>(v, 1ull << 30) : REACH_CHUNK;
+}
+
+// The level loop of gm_reach (reach_common.hpp).  The starts are uploaded in chunks and marked
+// at side 0 by a seed launch; then, per ply, the frontier is fed to the engine's level kernel
+// in chunks, the accumulator read back (one synchronisation per level: the next frontier's
+// size decides the next launches), and the two frontiers swapped.  The next frontier is sized
+// from what can still be marked and from the frontier's size times the move count.
+int reach_run(Ctx *c, const ReachReq &q, const ReachDims &dim, const std::function<int(const ReachDev &)> &level,
+              const std::function<int(const ReachDev &)> &sweep) {
+    const uint64_t KB = q.key_bytes, chunk = reach_chunk();
+    gm_reach_out_t o{};
+    q.ply_counts->clear();
+    q.keys->clear();
+    q.recs->clear();
+    q.sides->clear();
+    DevBuf<uint32_t> marks;
+    DevBuf<unsigned long long> acc;
+    const uint64_t words = std::max<uint64_t>(1, (dim.units + 15) / 16);
+    GM_TRY(marks.alloc(words));
+    GM_TRY(acc.alloc(RA_WORDS));
+    GM_HIP(hipMemsetAsync(marks, 0, words * 4, c->stream));
+    GM_HIP(hipMemsetAsync(acc, 0, RA_WORDS * 8, c->stream));
+    DevBuf<unsigned char> fr[2];
+    uint64_t have[2] = {0, 0};
+    auto need = [&](int w, uint64_t n) -> int {
+        if (have[w] >= n && fr[w].p) return GM_OK;
+        if (fr[w].p) { (void)hipFree(fr[w].p); fr[w].p = nullptr; }
+        GM_TRY(fr[w].alloc(std::max<uint64_t>(n, 1) * KB));
+        have[w] = n;
+        return GM_OK;
+    };
+    unsigned long long h[RA_WORDS];
+    auto read_acc = [&]() -> int {
+        GM_HIP(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));
+        if (h[RA_OVER]) { set_error("gm_reach: a frontier outgrew its bound"); return GM_E_STATE; }
+        return GM_OK;
+    };
+    ReachDev r{};
+    r.marks = marks;
+    r.acc = acc;
+    // the starts: marked themselves, at side 0
+    int cur = 0;
+    {
+        const uint64_t up = std::min(q.n_starts, chunk);
+        DevBuf<unsigned char> in;
+        GM_TRY(in.alloc(std::max<uint64_t>(up, 1) * KB));
+        r.next_cap = std::min(q.n_starts, dim.positions);
+        GM_TRY(need(cur, r.next_cap));
+        r.next = fr[cur].p;
+        r.seed = 1;
+        r.side = 0;
+        for (uint64_t s = 0; s < q.n_starts; s += up) {
+            r.m = std::min(up, q.n_starts - s);
+            GM_HIP(hipMemcpyAsync(in, (const unsigned char *)q.starts + s * KB, r.m * KB, hipMemcpyHostToDevice, c->stream));
+            r.in = in.p;
+            GM_TRY(level(r));
+        }
+        GM_TRY(read_acc());   // synchronised: `in` may leave scope
+        r.seed = 0;
+    }
+    uint64_t f = h[RA_CURSOR], marked = f;
+    if (f) q.ply_counts->push_back(h[RA_PAIRS]);
+    for (uint32_t ply = 0; f; ply++) {
+        if (q.how.max_plies && ply >= q.how.max_plies) break;
+        uint64_t bound = 2 * dim.positions - marked;
+        if (dim.max_moves) bound = std::min(bound, f * dim.max_moves);
+        if (!bound) break;   // every (position, side) is marked
+        GM_TRY(need(1 - cur, bound));
+        GM_HIP(hipMemsetAsync(acc, 0, 16, c->stream));   // the cursor and the level's pairs
+        r.next = fr[1 - cur].p;
+        r.next_cap = bound;
+        r.side = (ply + 1) & 1u;
+        r.policy = ply & 1u ? q.how.other : q.how.mover;
+        for (uint64_t s = 0; s < f; s += chunk) {
+            r.in = fr[cur].p + s * KB;
+            r.m = std::min(chunk, f - s);
+            GM_TRY(level(r));
+        }
+        GM_TRY(read_acc());
+        f = h[RA_CURSOR];
+        marked += f;
+        if (f) q.ply_counts->push_back(h[RA_PAIRS]);
+        cur = 1 - cur;
+    }
+    o.n = h[RA_FRESH];
+    for (size_t d = 0; d < q.ply_counts->size(); d++) (d & 1 ? o.n_other : o.n_mover) += (*q.ply_counts)[d];
+    o.n_starts = h[RA_STARTS];
+    o.edges = h[RA_EDGES];
+    o.missing = h[RA_MISSING];
+    o.plies = (int32_t)q.ply_counts->size();
+    *q.out = o;
+    const uint64_t want = std::min(q.cap, o.n);
+    if (!want) return GM_OK;
+    // the list: the frontiers go first, then one sweep over the marks
+    for (auto &b : fr)
+        if (b.p) { (void)hipFree(b.p); b.p = nullptr; }
+    DevBuf<unsigned char> dk, ds;
+    DevBuf<uint16_t> dr;
+    GM_TRY(dk.alloc(want * KB));
+    GM_TRY(dr.alloc(want));
+    GM_TRY(ds.alloc(want));
+    GM_HIP(hipMemsetAsync(acc, 0, 8, c->stream));
+    r.keys = dk.p;
+    r.recs = dr.p;
+    r.sides = ds.p;
+    r.cap = want;
+    GM_TRY(sweep(r));
+    GM_TRY(read_acc());
+    const uint64_t m = std::min<uint64_t>(h[RA_CURSOR], want);
+    q.keys->resize(m * KB);
+    q.recs->resize(m);
+    q.sides->resize(m);
+    if (m) {
+        GM_HIP(hipMemcpyAsync(q.keys->data(), dk, m * KB, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipMemcpyAsync(q.recs->data(), dr, m * 2, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipMemcpyAsync(q.sides->data(), ds, m, hipMemcpyDeviceToHost, c->stream));
+        GM_HIP(hipStreamSynchronize(c->stream));
     }
     return GM_OK;
 }
@@ -1011,6 +1140,68 @@ int gm_moves(gm_ctx *h, const uint64_t *key_words, uint64_t n, gm_moves_t *heads
         r.words = WIDE_WORDS;
     }
     return c->solved_by->moves(c, r);
+}
+
+int gm_reach(gm_ctx *h, const gm_reach_t *how, const uint64_t *start_words, uint64_t n_starts, gm_reach_out_t *out,
+             uint64_t *ply_counts, int ply_cap, uint64_t *key_words, uint16_t *records, uint8_t *sides, uint64_t cap) {
+    if (!h || !how || !out) { set_error("gm_reach: ctx, how or out is NULL"); return GM_E_ARG; }
+    if (how->mover > GM_REACH_FIRST || how->other > GM_REACH_FIRST) { set_error("gm_reach: a policy is not a GM_REACH_*"); return GM_E_ARG; }
+    if (how->reserved) { set_error("gm_reach: reserved is not 0"); return GM_E_ARG; }
+    if (n_starts && !start_words) { set_error("gm_reach: start_words is NULL"); return GM_E_ARG; }
+    GM_TRY(need_solved(h));
+    Ctx *c = &h->c;
+    GM_TRY(need_whole_table(c, "gm_reach"));
+    if (!c->solved_by->reach) { set_error("gm_reach: this engine's tables are not walked"); return GM_E_STATE; }
+    *out = gm_reach_out_t{};
+    std::vector<uint64_t> pc;
+    std::vector<unsigned char> raw;
+    std::vector<uint16_t> rr;
+    std::vector<uint8_t> ss;
+    if (n_starts) {
+        GM_HIP(hipSetDevice(c->device));
+        ReachReq q{*how, start_words, 8, n_starts, key_words ? cap : 0, out, &pc, &raw, &rr, &ss};
+        std::vector<K128> wide_keys;
+        if (c->wide) {
+            wide_keys.resize(n_starts);
+            for (uint64_t i = 0; i < n_starts; i++)
+                if (!DescOthello8::from_words(start_words + (size_t)WIDE_WORDS * i, &wide_keys[i]))
+                    wide_keys[i] = K128{0, 0};   // no valid key: skipped
+            q.starts = wide_keys.data();
+            q.key_bytes = sizeof(K128);
+        }
+        GM_TRY(c->solved_by->reach(c, q));
+    }
+    if (ply_counts && ply_cap > 0) {
+        if ((size_t)ply_cap < pc.size()) {
+            set_error("gm_reach: ply_counts holds %d plies, need %d", ply_cap, out->plies);
+            return GM_E_CAP;
+        }
+        for (int d = 0; d < ply_cap; d++) ply_counts[d] = (size_t)d < pc.size() ? pc[d] : 0;
+    }
+    // ascending ABI key order (a wide key: the position string as one integer)
+    const uint64_t m = rr.size();
+    if (!m) return GM_OK;
+    const int W = c->wide ? WIDE_WORDS : 1;
+    std::vector<uint64_t> w((size_t)W * m);
+    for (uint64_t i = 0; i < m; i++) {
+        if (c->wide) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
+        else w[i] = ((const uint64_t *)raw.data())[i];
+    }
+    std::vector<uint64_t> idx(m);
+    for (uint64_t i = 0; i < m; i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+        for (int j = W - 1; j >= 0; j--) {
+            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
+            if (x != y) return x < y;
+        }
+        return false;
+    });
+    for (uint64_t i = 0; i < m; i++) {
+        for (int j = 0; j < W; j++) key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
+        if (records) records[i] = rr[idx[i]];
+        if (sides) sides[i] = ss[idx[i]];
+    }
+    return GM_OK;
 }
 
 int gm_poke(gm_ctx *h, const uint64_t *key_words, uint16_t record) {

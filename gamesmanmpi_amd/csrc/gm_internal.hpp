@@ -65,6 +65,7 @@ struct Hist;   // hist_common.hpp: counts by value and remoteness (gm_histogram)
 struct VerifyDev;   // verify_common.hpp: the device accumulator of gm_verify
 struct SelectDev;   // select_common.hpp: the filter and the device accumulator of gm_select
 struct MovesReq;    // moves_common.hpp: the keys and the output arrays of gm_moves
+struct ReachReq;    // reach_common.hpp: the starts, the policies and the outputs of gm_reach
 struct ByteTables;  // byte_tables.hpp: where a byte-table SUBTRACT engine keeps its 1-byte codes
 struct Engine;
 
@@ -150,7 +151,7 @@ struct Ctx {
 // One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
 // record next to its functions; gm_solve picks one per solve from the context's options
 // (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
-// of the solved table (export, query, digest, histogram, select, verify, moves, dense table, rank stats) goes through it.
+// of the solved table (export, query, digest, histogram, select, verify, moves, reach, dense table, rank stats) goes through it.
 struct Engine {
     int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
     int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
@@ -174,6 +175,9 @@ struct Engine {
     // readers of byte_tables.hpp (the byte_* entries of their records) work from, reached through
     // Ctx::solved_by.  null: another engine
     void (*bytes)(Ctx *c, ByteTables *t);
+    // gm_reach: the closure of the request's starts under its move policies, level by level over
+    // the engine's own marks (reach_common.hpp)
+    int (*reach)(Ctx *c, const ReachReq &q);
 };
 // A record is host data, defined in the host pass only: the device pass of a translation unit
 // would emit a const record too, with references to the host functions it names.

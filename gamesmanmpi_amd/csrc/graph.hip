@@ -19,6 +19,7 @@
 #include "hist_common.hpp"
 #include "verify_common.hpp"
 #include "moves_common.hpp"
+#include "reach_common.hpp"
 #include "select_common.hpp"
 
 #include <algorithm>
@@ -335,6 +336,55 @@ static int graph_moves(Ctx *c, const MovesReq &r) {
     });
 }
 
+// gm_reach over node indices (reach_common.hpp): the mark index is the node, the children are
+// the whole CSR row in its order, a key >= n or a node without a score has no record.  A loopy
+// table's cycles end at the marks.
+struct ReachGraph {
+    using Key = uint64_t;
+    const uint8_t *prim;
+    const uint64_t *off;
+    const uint32_t *kid;
+    const uint16_t *score;
+    uint64_t n;
+    __device__ __forceinline__ int64_t find(const uint64_t &k, uint16_t &rec, uint64_t &st) const {
+        st = k;
+        rec = k < n ? graph_record(score[k]) : REC_UNSOLVED;
+        return rec == REC_UNSOLVED ? -1 : (int64_t)k;
+    }
+    __device__ __forceinline__ bool interior(const uint64_t &k) const { return prim[k] == UNDECIDED; }
+    template <class F>
+    __device__ __forceinline__ void visit(const uint64_t &k, F &&f) const {
+        const uint64_t e0 = off[k], e1 = off[k + 1];
+        for (uint64_t e = e0; e < e1; e++) f((uint64_t)kid[e], (uint32_t)(e - e0));
+    }
+    __device__ __forceinline__ uint32_t weight(const uint64_t &) const { return 1u; }
+};
+
+__global__ __launch_bounds__(256) void graph_reach_sweep_kernel(ReachGraph a, ReachDev r) {
+    for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < a.n; k += (uint64_t)gridDim.x * 256ull) {
+        const uint32_t bits = reach_bits(r, k);
+        if (bits) reach_emit(r, k, graph_record(a.score[k]), bits);
+    }
+}
+
+static int graph_reach(Ctx *c, const ReachReq &q) {
+    Graph *g = c->graph;
+    const ReachGraph acc{g->prim, g->off, g->kid, g->score, g->n};
+    // a row's length is not bounded here: the marks alone size the frontiers
+    return reach_run(
+        c, q, ReachDims{g->n, g->n, 0},
+        [&](const ReachDev &r) {
+            hipLaunchKernelGGL(reach_level_kernel<ReachGraph>, dim3(grid_counted(r.m)), dim3(256), 0, c->stream, acc, r);
+            GM_HIP(hipGetLastError());
+            return GM_OK;
+        },
+        [&](const ReachDev &r) {
+            hipLaunchKernelGGL(graph_reach_sweep_kernel, dim3(grid_counted(g->n)), dim3(256), 0, c->stream, acc, r);
+            GM_HIP(hipGetLastError());
+            return GM_OK;
+        });
+}
+
 static int graph_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     Graph *g = c->graph;
     if (words[0] >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
@@ -358,6 +408,6 @@ void graph_free(Ctx *c) {
 
 GM_ENGINE_RECORD(graph_engine, GM_ENGINE_GRAPH, nullptr, graph_export,
                  graph_query, graph_digest, graph_histogram, graph_select, nullptr, graph_free, graph_verify, graph_poke,
-                 nullptr, graph_moves)
+                 nullptr, graph_moves, nullptr, graph_reach)
 
 }  // namespace gm

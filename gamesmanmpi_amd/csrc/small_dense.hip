@@ -10,6 +10,7 @@
 #include "hist_common.hpp"
 #include "verify_common.hpp"
 #include "moves_common.hpp"
+#include "reach_common.hpp"
 #include "select_common.hpp"
 
 namespace gm {
@@ -206,6 +207,12 @@ static int small_dense_moves(Ctx *c, const MovesReq &r) {
     return moves_host(c->ttt, r, [&](uint64_t k) { return k < s->slots ? s->h_rec[k] : REC_UNSOLVED; });
 }
 
+// gm_reach from the same host records (reach_common.hpp reach_host)
+static int small_dense_reach(Ctx *c, const ReachReq &q) {
+    SmallDense *s = c->sd;
+    return reach_host(c->ttt, q, s->slots, [&](uint64_t k) { return k < s->slots ? s->h_rec[k] : REC_UNSOLVED; });
+}
+
 static int small_dense_verify(Ctx *c, const VerifyDev &v) {
     SmallDense *s = c->sd;
     hipLaunchKernelGGL(small_verify_kernel<DescTTT>, dim3(grid_counted(s->slots)), dim3(256), 0, c->stream, c->ttt,
@@ -280,6 +287,7 @@ static int small_dense_import(Ctx *c, const void *keys_, const uint16_t *recs, u
 
 GM_ENGINE_RECORD(small_dense_engine, GM_ENGINE_DENSE, small_dense_solve, small_dense_export,
                  small_dense_query, small_dense_digest, small_dense_histogram, small_dense_select, nullptr, small_dense_free,
-                 small_dense_verify, small_dense_poke, small_dense_import, small_dense_moves)
+                 small_dense_verify, small_dense_poke, small_dense_import, small_dense_moves, nullptr,
+                 small_dense_reach)
 
 }  // namespace gm

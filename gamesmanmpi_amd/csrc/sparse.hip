@@ -860,6 +860,12 @@ static int sparse_moves(Ctx *c, const MovesReq &r) {
     });
 }
 
+static int sparse_reach(Ctx *c, const ReachReq &q) {
+    return with_desc(c, [&](const auto &d) {
+        return tiers_reach(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, q);
+    });
+}
+
 static int sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
     return with_desc(c, [&](const auto &d) {
         return tiers_poke(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, words[0], rec);
@@ -897,6 +903,6 @@ static int sparse_import(Ctx *c, const void *keys, const uint16_t *recs, uint64_
 
 GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
                  sparse_query, sparse_digest, sparse_histogram, sparse_select, nullptr, sparse_free, sparse_verify, sparse_poke,
-                 sparse_import, sparse_moves)
+                 sparse_import, sparse_moves, nullptr, sparse_reach)
 
 }  // namespace gm

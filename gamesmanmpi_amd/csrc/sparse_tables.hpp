@@ -18,6 +18,7 @@
 #include "sparse_common.hpp"
 #include "verify_common.hpp"
 #include "moves_common.hpp"
+#include "reach_common.hpp"
 #include "select_common.hpp"
 
 namespace gm {
@@ -580,6 +581,68 @@ __global__ __launch_bounds__(256) void res_moves_kernel(D d, TierTabs<key_t<D>> 
         moves_of_key(d, tab, mv, i);
 }
 
+// gm_reach over tier tables (reach_common.hpp): the accessor of reach_level_kernel.  The mark
+// index of a key is the slot of its representative in its owner's table of its tier plus that
+// table's base, a prefix sum of the capacities over the G x ntabs matrix.  The children are the
+// plugin's own (the unreduced descriptor, as gm_moves), each brought to its representative by
+// the lookup; a frontier holds representatives.
+template <class D>
+struct ReachTiers {
+    using Key = key_t<D>;
+    D d;
+    const typename KT<Key>::Res *tabs;
+    const uint64_t *base;
+    int G, ntabs;
+    int64_t t_root;
+    __device__ __forceinline__ int64_t find(const Key &k, uint16_t &rec, Key &st) const {
+        rec = REC_UNSOLVED;
+        st = k;
+        if (!d.valid(k)) return -1;
+        const int64_t t = d.tier(k) - t_root;
+        if (t < 0 || t >= ntabs) return -1;
+        st = d.canon(k);
+        const size_t tb = (size_t)owner_rank(st, (uint32_t)G) * ntabs + (size_t)t;
+        const typename KT<Key>::Res T = tabs[tb];
+        const int64_t at = res_find_slot(T, st);
+        if (at < 0) return -1;
+        rec = record_of_score((uint16_t)slot_score(T.s[at]));
+        return rec == REC_UNSOLVED ? -1 : (int64_t)(base[tb] + (uint64_t)at);
+    }
+    __device__ __forceinline__ bool interior(const Key &k) const { return d.primitive(k) == UNDECIDED; }
+    template <class F>
+    __device__ __forceinline__ void visit(const Key &k, F &&f) const {
+        const auto plain = unreduced(d);
+        uint32_t seq = 0;
+        plain.visit(k, [&](const Key &ch) {
+            uint32_t pos = seq++;
+            if constexpr (slot_order_t<D>::value) pos = (uint32_t)move_slot(plain, k, ch);
+            f(ch, pos);
+            return true;
+        });
+    }
+    __device__ __forceinline__ uint32_t weight(const Key &st) const {
+        uint32_t w = 0;
+        d.orbit(st, [&](const Key &) { w++; });
+        return w;
+    }
+};
+
+// the sweep over one table: every marked representative emits each member of its orbit with
+// the representative's record and side bits, as res_select_kernel emits a match
+template <class D>
+__global__ __launch_bounds__(256) void res_reach_sweep_kernel(D d, const typename KT<key_t<D>>::Slot *__restrict__ sl,
+                                                              uint64_t cap, uint64_t base, ReachDev r) {
+    using K = key_t<D>;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * 256ull) {
+        const K key = slot_key(sl[i]);
+        if (key_empty(key)) continue;
+        const uint32_t bits = reach_bits(r, base + i);
+        if (!bits) continue;
+        const uint16_t rec = record_of_score((uint16_t)slot_score(sl[i]));
+        d.orbit(key, [&](const K &k) { reach_emit(r, k, rec, bits); });
+    }
+}
+
 // gm_poke: the score of key's slot overwritten, or (remove) the slot emptied; *found = 1 if held
 template <class K>
 __global__ void res_poke_kernel(typename KT<K>::Res t, K key, uint64_t score, int remove, uint32_t *found) {
@@ -886,6 +949,59 @@ inline int tiers_moves(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>
         GM_HIP(hipGetLastError());
         return GM_OK;
     });   // moves_run ends synchronised: tabs may leave scope
+}
+
+// whether the tables hold one representative per orbit (games.hpp: the descriptor's sym, set per solve)
+template <class D>
+inline bool tables_reduced(const D &) { return false; }
+inline bool tables_reduced(const DescToot &d) { return d.sym != 0; }
+inline bool tables_reduced(const DescOthello &d) { return d.sym != 0; }
+
+// gm_reach over tier tables: group g holds the keys of owner rank g (one group: the one-GPU engine)
+template <class D>
+inline int tiers_reach(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>> &groups, const ReachReq &q) {
+    using K = key_t<D>;
+    if (reach_wants_first(q) && tables_reduced(d)) {
+        set_error("gm_reach: GM_REACH_FIRST does not commute with the symmetries and this table holds one "
+                  "representative per orbit: solve with GM_OPT_SYMMETRY 0");
+        return GM_E_ARG;
+    }
+    DevBuf<typename KT<K>::Res> tabs;
+    int ntabs = 0;
+    GM_TRY(tiers_matrix<K>(c, groups, &tabs, &ntabs));
+    // every table's first mark index
+    std::vector<uint64_t> base(std::max<size_t>(1, groups.size() * (size_t)ntabs), 0);
+    uint64_t units = 0;
+    for (size_t g = 0; g < groups.size(); g++)
+        for (size_t t = 0; t < (size_t)ntabs; t++) {
+            base[g * ntabs + t] = units;
+            if (t < groups[g].tiers->size() && (*groups[g].tiers)[t].slots) units += (*groups[g].tiers)[t].cap;
+        }
+    DevBuf<uint64_t> dbase;
+    GM_TRY(dbase.alloc(base.size()));
+    GM_HIP(hipMemcpyAsync(dbase, base.data(), base.size() * 8, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipStreamSynchronize(c->stream));
+    const ReachTiers<D> acc{d, tabs.p, dbase.p, (int)groups.size(), ntabs, groups.empty() ? 0 : groups[0].t_root};
+    // the capacities bound what can be marked
+    return reach_run(
+        c, q, ReachDims{units, units, (uint64_t)D::MAXC},
+        [&](const ReachDev &r) {
+            // random probes whose workgroups finish unevenly: grid_for's 8,192, as res_moves_kernel
+            hipLaunchKernelGGL(reach_level_kernel<ReachTiers<D>>, dim3(grid_for(r.m)), dim3(256), 0, c->stream, acc, r);
+            GM_HIP(hipGetLastError());
+            return GM_OK;
+        },
+        [&](const ReachDev &r) {
+            for (size_t g = 0; g < groups.size(); g++)
+                for (size_t t = 0; t < groups[g].tiers->size(); t++) {
+                    const SpTierT<K> &T = (*groups[g].tiers)[t];
+                    if (!T.slots || !T.cap) continue;
+                    hipLaunchKernelGGL(res_reach_sweep_kernel<D>, dim3(grid_counted(T.cap)), dim3(256), 0, c->stream, d,
+                                       T.slots, T.cap, base[g * ntabs + t], r);
+                }
+            GM_HIP(hipGetLastError());
+            return GM_OK;
+        });   // reach_run ends synchronised: tabs and dbase may leave scope
 }
 
 // gm_poke in tier tables: the representative's slot in its owner's table of its tier

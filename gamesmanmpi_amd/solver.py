@@ -277,6 +277,39 @@ class Context:
         t = total.value
         return heads, (ck[:t] if self.words > 1 else ck[:t, 0]), cr[:t]
 
+    def reach(self, starts, mover=_lib.REACH_ALL, other=_lib.REACH_ALL, max_plies=0, cap=0, plies=True):
+        """gm_reach: the positions reachable from `starts` (keys as query() takes them) when the
+        starts' mover follows policy `mover` and the opponent `other` (_lib.REACH_*), found on
+        the device.  Returns (out, ply_counts, keys, records, sides): out the dict of
+        gm_reach_out_t, ply_counts a uint64 array with one entry per ply reached (None with
+        plies=False), keys up to `cap` reached positions ascending as export() returns them,
+        records their u16 records and sides their side bits (bit 0 an even ply, bit 1 an odd
+        one).  cap=0: counts only (keys, records and sides None)."""
+        keys = self.key_array(starts)
+        n = len(keys)
+        how = _lib.Reach(int(mover), int(other), int(max_plies), 0)
+        out = _lib.ReachOut()
+        cap = int(cap)
+        kw = np.zeros((max(1, cap), self.words), dtype=np.uint64)
+        rr = np.zeros(max(1, cap), dtype=np.uint16)
+        ss = np.zeros(max(1, cap), dtype=np.uint8)
+        ply_cap = 1024 if plies else 0
+        while True:
+            pc = np.zeros(max(1, ply_cap), dtype=np.uint64)
+            rc = self.L.gm_reach(self.h, ctypes.byref(how), keys.ctypes.data if n else None, n, ctypes.byref(out),
+                                 pc.ctypes.data if ply_cap else None, ply_cap, kw.ctypes.data if cap else None,
+                                 rr.ctypes.data if cap else None, ss.ctypes.data if cap else None, cap)
+            if rc == -8 and out.plies > ply_cap:   # GM_E_CAP: out is set
+                ply_cap = out.plies
+                continue
+            _lib.check(rc)
+            break
+        pcs = pc[:out.plies].copy() if plies else None
+        if not cap:
+            return out.as_dict(), pcs, None, None, None
+        m = min(cap, out.n)
+        return out.as_dict(), pcs, (kw[:m] if self.words > 1 else kw[:m, 0]), rr[:m], ss[:m]
+
     def stats(self):
         s = _lib.Stats()
         _lib.check(self.L.gm_stats(self.h, ctypes.byref(s)))
@@ -450,6 +483,64 @@ class Solver:
         """Check the solved table against the game rules on the device (gm_verify):
         (counts dict, up to `cap` offending keys)."""
         return self.ctx.verify(cap)
+
+    def reach(self, positions=None, mover="all", other="all", max_plies=0, cap=0):
+        """The positions reachable from `positions` (default: the root) when their mover follows
+        policy `mover` and the opponent `other` ("all", "best", "first"), found on the device
+        (gm_reach).  Returns the dict of gm_reach_out_t with "ply_counts" (positions first
+        reached per ply), "share" (n over n_positions) and, with cap > 0, "positions": up to
+        `cap` rows (position, value, remoteness, side bits), ascending by key.  The nodes of a
+        graph solve with symmetry generators are orbit representatives: their counts are
+        weighted by orbit size here, as find() weights them."""
+        from . import reach as R
+        starts = [self.codec.key(p) for p in ([self.root] if positions is None else positions)]
+        pm, po = R.policy(mover), R.policy(other)
+        weighted = self.codec.game_id == _lib.GAME_GRAPH and bool(self.codec.gens)
+        want = max(int(cap), self.ctx.stats()["n_positions"]) if weighted else int(cap)
+        out, pcs, keys, recs, sides = self.ctx.reach(starts, pm, po, max_plies, want)
+        pcs = [int(x) for x in pcs]
+        if weighted:
+            w = {int(k): len(self.codec.members(int(k))) for k in keys}
+            out["n"] = sum(w.values())
+            out["n_mover"] = sum(w[int(k)] for k, s in zip(keys, sides) if s & 1)
+            out["n_other"] = sum(w[int(k)] for k, s in zip(keys, sides) if s & 2)
+            # a ply's pairs: what a search bounded at that ply adds to the one bounded a ply earlier
+            seen, pcs = set(), []
+            for d in range(out["plies"]):
+                if d == 0:
+                    pairs = {(int(k), 0) for k in starts if int(k) in w}
+                else:
+                    _, _, kd, _, sd = self.ctx.reach(starts, pm, po, d, want)
+                    pairs = {(int(k), b) for k, s in zip(kd, sd) for b in (0, 1) if s >> b & 1}
+                pcs.append(sum(w[k] for k, _ in pairs - seen))
+                seen |= pairs
+        out["ply_counts"] = pcs
+        out["share"] = out["n"] / self.n_positions if self.n_positions else 0.0
+        if cap:
+            m = min(int(cap), len(recs))
+            ks = [int(k) for k in keys[:m]] if self.ctx.words == 1 else [_lib.words_to_int(k) for k in keys[:m]]
+            out["positions"] = [(self.codec.pos(k),) + split_record(r) + (int(s),)
+                                for k, r, s in zip(ks, recs[:m], sides[:m])]
+        return out
+
+    def strategy(self, pos=None, side=None, first=False):
+        """The weak solution inside the strong one: the positions that can occur from `pos`
+        (default: the root) when one side plays perfectly -- every optimal move, or with
+        first=True the one move the solver plays -- and the other side plays anything.  `side`
+        is "mover" (the player to move at `pos`) or "other"; it defaults to the side that does
+        not lose at `pos`: the mover for WIN / TIE / DRAW, the opponent for LOSS.  Returns
+        reach()'s dict with "side" and "value" (of `pos`)."""
+        pos = self.root if pos is None else pos
+        value = self.lookup(pos)[0]
+        if side is None:
+            side = "other" if value == LOSS else "mover"
+        if side not in ("mover", "other"):
+            raise ValueError("side is 'mover' or 'other'")
+        perfect = "first" if first else "best"
+        out = self.reach([pos], mover=perfect if side == "mover" else "all",
+                         other=perfect if side == "other" else "all")
+        out["side"], out["value"] = side, value
+        return out
 
     def moves(self, pos):
         """The moves at `pos` and what each is worth: rows (move, child position, value,

@@ -518,6 +518,76 @@ typedef struct {
 int gm_moves(gm_ctx *ctx, const uint64_t *key_words, uint64_t n, gm_moves_t *heads, uint64_t *child_words,
              uint16_t *child_records, uint64_t cap, uint64_t *n_children);
 
+/* The move policy of one side in gm_reach: every move, every optimal move (gm_moves' n_best
+ * children), or the one move gm_moves reports as best. */
+enum { GM_REACH_ALL = 0, GM_REACH_BEST = 1, GM_REACH_FIRST = 2 };
+typedef struct {
+    uint32_t mover;      /* policy of the player to move at the start positions (even plies) */
+    uint32_t other;      /* policy of the opponent (odd plies) */
+    uint32_t max_plies;  /* 0: no bound; else positions first reached at ply max_plies are not expanded */
+    uint32_t reserved;   /* 0 */
+} gm_reach_t;            /* 16 bytes */
+typedef struct {
+    uint64_t n;          /* distinct positions reached, starts included */
+    uint64_t n_mover;    /* reached with the starts' mover to move (an even ply) */
+    uint64_t n_other;    /* reached at an odd ply; n_mover + n_other - n were reached both ways */
+    uint64_t n_starts;   /* start keys given that have a record (repeats counted) */
+    uint64_t edges;      /* selected moves followed = child lookups made for marking */
+    uint64_t missing;    /* selected children without a record (0 on a table gm_verify passes) */
+    int32_t  plies;      /* 1 + the largest ply at which a (position, side) was first reached; 0 if none */
+    int32_t  reserved;
+} gm_reach_out_t;        /* 56 bytes */
+
+/* The positions reachable from a set of start positions when each side follows a move policy:
+ * a forward breadth-first closure over the solved table, on the device -- gm_moves' edge pass
+ * (parent -> children -> records) run level by level with a visited set in place of an output
+ * array.  ALL / ALL from a position is the subgame below it; BEST (or FIRST) for one side and
+ * ALL for the other is the weak solution inside the strong one, the positions a perfect player
+ * of that side can meet.
+ * Side: the value algebra alternates the mover on every edge, so the side of a reached position
+ * is the parity of the ply at which it is reached.  A position may be reached at both parities
+ * (the subtraction game's keys carry no turn), so the visited set is over (position, side).
+ * Ply d of the search holds the pairs first reached at ply d; ply_counts[d] is their number.
+ * Which children are followed: a pair at ply d is expanded when its position has a record, is
+ * not primitive and max_plies does not forbid it.  Its children are exactly gm_moves' children
+ * (the plugin's gen_moves order, the unreduced descriptor, Othello's pass child; on a
+ * GM_GAME_GRAPH context the whole CSR row, without gm_moves' limit of 32,767).  The policy of
+ * the side to move selects among them: ALL every child, BEST every child whose rank equals the
+ * maximum, FIRST the one child gm_moves reports as best.  Ranks are gm_moves': LOSS (shortest) >
+ * TIE (shortest) > DRAW > WIN (longest) > no record.  The marks end the search, so the DRAW
+ * positions and the cycles of a loopy table need nothing special.  A selected child without a
+ * record counts in missing, is not marked and is not expanded.
+ * Starts: n_starts keys of gm_key_words() words each, in any order, repeats allowed.  A start
+ * that is invalid, outside the region or without a record is skipped; it is no error.
+ * Symmetry reduction: marks live on the stored representative; every count (n, n_mover, n_other,
+ * ply_counts) is weighted by orbit size, as gm_histogram counts, and the key list holds every
+ * orbit member with the representative's record and side bits, as gm_select lists them.  The
+ * result is the closure of the reached set under the root's symmetry group.  ALL and BEST commute
+ * with the symmetries: their result equals the unreduced one whenever the starts are closed under
+ * the group, which the root alone always is (edges and missing count the lookups made, from one
+ * representative per orbit).  FIRST does not: on a table that holds one
+ * representative per orbit FIRST is GM_E_ARG (solve with GM_OPT_SYMMETRY 0).  Graph contexts
+ * know no symmetry on the device.
+ * Output: out is always filled.  ply_counts == NULL or ply_cap == 0: not written; ply_cap <
+ * out->plies: GM_E_CAP with out still filled; entries [plies, ply_cap) are zeroed.  The key
+ * list holds up to cap reached positions, ascending in gm_export / gm_export_key order and
+ * distinct: all of them when out->n <= cap, else any cap of them; records and sides (bit 0: an
+ * even ply, bit 1: an odd ply) may each be NULL.  key_words == NULL or cap == 0: counts only,
+ * and nothing but out and ply_counts leaves the device.
+ * GM_E_ARG (checked first): how or out is NULL, a policy above 2, reserved != 0, n_starts > 0
+ * with start_words NULL.  n_starts == 0: GM_OK with zero counts.  GM_E_STATE before a solve,
+ * after a failed solve or import, and on a rank of a multi-process solve (as gm_verify and
+ * gm_moves; virtual ranks are answered as one table).  The call changes no table and keeps no
+ * state; a kept histogram stays kept.
+ * A frontier is processed in chunks (GM_REACH_CHUNK entries, a development variable; default
+ * 2^20).  Device memory: two mark bits per table slot (byte tables: per key of the heaps'
+ * lattice, 1 GiB at 8 heaps; a graph: per node) and two frontiers of keys.
+ * Replaces reopening the `resolved` shelves and walking the plugin ply by ply on the host
+ * (src/cache_dict.py:38-79, src/game_state.py:33-41). */
+int gm_reach(gm_ctx *ctx, const gm_reach_t *how, const uint64_t *start_words, uint64_t n_starts,
+             gm_reach_out_t *out, uint64_t *ply_counts, int ply_cap,
+             uint64_t *key_words, uint16_t *records, uint8_t *sides, uint64_t cap);
+
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 

@@ -3,6 +3,7 @@
 
     python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
                           [--loopy] [--load DIR] [--find SPEC ...] [--find-cap N] [--line] [--moves]
+                          [--strategy [best|first]]
 
 The reference (solve_local.py:4-72) loads the plugin by path, solves it in one
 process and prints "Winning position", "Losing position", "Tie" or "Draw"
@@ -20,6 +21,10 @@ gamesmanmpi_amd/find.py; a bad spec exits 2 before the solve), and ``--line`` th
 variation from the root, one row per ply.  ``--moves`` prints ``Moves:`` and the root's moves, each
 with its child position and value and a trailing `` *`` on every optimal one; with ``--find`` every
 position found is followed by its own moves instead (gm_moves, gamesmanmpi_amd/moves.py).
+``--strategy [best|first]`` prints, after the root line, how many positions can occur when the side
+that does not lose at the root plays perfectly and the other plays anything (gm_reach,
+gamesmanmpi_amd/reach.py), then the positions first reached per ply; ``first`` on a solve that stores
+one representative per symmetry orbit says so and exits 1.
 ``--loopy`` solves a game in which positions can repeat (explicit graph, GM_OPT_LOOPY): "Draw"
 is then a real answer, ``--remoteness`` prints ``DRAW`` alone for it and ``--analysis`` adds a
 line ``Draw  N`` under its table.  ``--load DIR`` takes the place of the solve: the
@@ -57,6 +62,8 @@ def build_parser():
     p.add_argument("--line", action="store_true", help="print the principal variation from the root")
     p.add_argument("--moves", action="store_true",
                    help="print the root's moves with their values, or with --find the moves of every position found")
+    p.add_argument("--strategy", nargs="?", const="best", choices=("best", "first"), metavar="best|first",
+                   help="print how many positions can occur when the side that does not lose at the root plays perfectly")
     p.add_argument("--loopy", action="store_true")
     p.add_argument("--load", metavar="DIR",
                    help="in place of the solve, load the table.npz files a solver_launcher.py -sd DIR run wrote")
@@ -99,6 +106,9 @@ def main(argv=None):
     print(MESSAGES[s.value])
     if args.remoteness:
         print(s.root_line())
+    if args.strategy and not solver_launcher.write_strategy(s, args.strategy, sys.stdout):
+        s.close()
+        return 1
     if args.analysis:
         from gamesmanmpi_amd import analysis
         print(analysis.format_table(s.analysis()))

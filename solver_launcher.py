@@ -55,6 +55,14 @@ Differences, on purpose:
   spaces, all of them valued by one device call (gm_moves, gamesmanmpi_amd/moves.py).  A solve
   sharded over processes goes ahead without the moves and says so in one line on stderr: no
   rank holds the whole table (``--load DIR`` of its ``-sd`` output does);
+* ``--strategy [best|first]`` prints, right after the root line, ``Strategy for the <side> (root
+  <root line>): N of TOTAL positions (S%), deepest ply D`` and one line ``  ply K: COUNT`` per ply:
+  the positions that can occur when the side that does not lose at the root plays perfectly
+  (``best``: every optimal move, ``first``: the one move the solver plays) and the other side
+  plays anything, found on the device (gm_reach, gamesmanmpi_amd/reach.py).  ``first`` on a solve
+  that stores one representative per symmetry orbit says so on stderr and exits 1; a solve
+  sharded over processes is refused (exit status 2).  Combines with ``--loopy`` and ``--load``
+  as ``--moves`` does;
 * ``--loopy`` is for games in which a position can repeat: the plugin is enumerated on the
   host and solved as an explicit graph with cycles allowed (GM_OPT_LOOPY, one process); a
   position neither side can decide is a draw, the root line of a drawn root is ``DRAW``
@@ -112,6 +120,9 @@ def build_parser():
     p.add_argument("--line", action="store_true", help="after the root line, print the principal variation from the root")
     p.add_argument("--moves", action="store_true",
                    help="print the root's moves with their values, or with --find the moves of every position found")
+    p.add_argument("--strategy", nargs="?", const="best", choices=("best", "first"), metavar="best|first",
+                   help="print how many positions can occur when the side that does not lose at the root plays "
+                        "perfectly (best: every optimal move; first: the one move the solver plays)")
     p.add_argument("--loopy", action="store_true",
                    help="solve a game with cycles: explicit graph, undecidable positions are DRAW")
     p.add_argument("--load", metavar="DIR",
@@ -239,6 +250,11 @@ def run(args, out=sys.stdout):
                 print("--moves needs the whole table in one process: this solve is sharded over %d processes; solve "
                       "with -sd DIR, then ask for the moves of the stored table (--load DIR)" % world, file=sys.stderr)
             args.moves = False
+        if plan == "sharded" and getattr(args, "strategy", None):
+            if rank == 0:
+                print("--strategy needs the whole table in one process: this solve is sharded over %d processes.  Run "
+                      "it on one process (virtual ranks included)." % world, file=sys.stderr)
+            return 2
         if plan == "sharded" and getattr(args, "load", None):
             if rank == 0:
                 print("--load builds the whole table in one process: run it on one process, or with more ranks than "
@@ -306,6 +322,11 @@ def _solve_and_report(args, game, root, rank, world, local, plan, out):
     if rank == 0:
         out.write(solver.root_line() + "\n")
         out.flush()
+    if getattr(args, "strategy", None) and rank == 0 and not write_strategy(solver, args.strategy, out):
+        solver.close()
+        if plan == "single":
+            dist.release_waiters(world, ok=False)
+        return 1
     if getattr(args, "analysis", False):
         report_analysis(args, solver, rank, world, plan, out)
     if find_specs(args):
@@ -359,6 +380,28 @@ def write_moves(solver, out):
     for ln in moves.format_block(rows):
         out.write(ln + "\n")
     out.flush()
+
+
+def write_strategy(solver, mode, out):
+    """--strategy: the positions that can occur when the side that does not lose at the root
+    plays perfectly and the other plays anything (gm_reach through Solver.strategy): one line,
+    then the positions first reached per ply.  False when the table cannot answer: "first" on a
+    solve that stores one representative per symmetry orbit."""
+    from gamesmanmpi_amd import _lib, reach
+    try:
+        s = solver.strategy(first=mode == "first")
+    except _lib.GMError as e:
+        if e.code != -1:
+            raise
+        print("--strategy first follows one move per position, which the symmetry reduction of this solve does not "
+              "preserve: rerun with the reduction off (GM_OPT_SYMMETRY 0), or ask for --strategy best",
+              file=sys.stderr)
+        return False
+    side = "player to move" if s["side"] == "mover" else "opponent"
+    for ln in reach.format_strategy(side, solver.root_line(), s, solver.n_positions, s["ply_counts"]):
+        out.write(ln + "\n")
+    out.flush()
+    return True
 
 
 def report_analysis(args, solver, rank, world, plan, out):
