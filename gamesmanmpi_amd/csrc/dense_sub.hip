@@ -1156,6 +1156,23 @@ static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap
         set_error("export buffer holds %llu, need %llu", (unsigned long long)cap, (unsigned long long)c->n_positions);
         return GM_E_CAP;
     }
+    // A small region of a large table (a custom root): its keys are asked of the device, so the
+    // cost follows the region.  Copying and walking the table took 8 heaps' 4 GiB for any root.
+    const uint64_t region = sub_region_size(c->root, d->heaps);
+    if (region <= d->slots / 16) {
+        std::vector<uint64_t> ks(region);
+        std::vector<uint16_t> rs(region);
+        box_region_keys(c->root, ks.data(), region);
+        GM_TRY(byte_query(c, ks.data(), rs.data(), region));
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < region && j < cap; i++) {
+            if (rs[i] == REC_UNSOLVED) continue;   // code 0, as below
+            keys[j] = ks[i];
+            recs[j] = rs[i];
+            j++;
+        }
+        return GM_OK;
+    }
     std::vector<uint8_t> h(d->slots);
     GM_HIP(hipMemcpy(h.data(), d->table, d->slots, hipMemcpyDeviceToHost));
     uint64_t j = 0;

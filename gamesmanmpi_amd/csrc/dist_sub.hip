@@ -733,6 +733,17 @@ static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap,
     DistSub *d = c->dist_sub;
     hipStream_t H = c->stream;
     const uint64_t bsz = 1ull << (4 * d->low);
+    // Virtual ranks together hold the root's region.  A small region of a large table (a custom
+    // root): its keys are asked of the device, each read from its block's owner, so the cost
+    // follows the region.  Copying and walking every rank's blocks took 8 heaps' 4 GiB for any root.
+    const uint64_t region = sub_region_size(c->root, d->heaps);
+    if (d->loopback && region <= (1ull << (4 * d->heaps)) / 16) {
+        *n = region;
+        if (!keys) return GM_OK;
+        if (cap < region) { set_error("export buffer too small"); return GM_E_CAP; }
+        box_region_keys(c->root, keys, region);
+        return byte_query(c, keys, recs, region);
+    }
     std::vector<std::pair<uint64_t, uint16_t>> out;
     uint64_t total = 0;
     for (auto &R : d->ranks) {

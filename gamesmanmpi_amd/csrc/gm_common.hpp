@@ -100,6 +100,11 @@ GM_HD bool sub_in_region(uint64_t key, uint64_t root, int heaps) {
     for (int j = 0; j < heaps; j++) in &= ((key >> (4 * j)) & 15u) <= ((root >> (4 * j)) & 15u);
     return in;
 }
+GM_HD uint64_t sub_region_size(uint64_t root, int heaps) {
+    uint64_t n = 1;
+    for (int j = 0; j < heaps; j++) n *= ((root >> (4 * j)) & 15u) + 1u;
+    return n;
+}
 
 GM_HD uint64_t mix64(uint64_t x) {
     x ^= x >> 33;

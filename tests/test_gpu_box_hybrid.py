@@ -21,7 +21,6 @@ either end, so clipped to T they are (lo, T - 1 - lo), or every tier in the head
 2 lo >= T (where that holds for all of them, T // 3 tiers at either end is run as well); plus 41,40 (every tier in dataflow
 launches) and one range whose tail is the last tier alone.
 """
-import ctypes
 import functools
 import json
 import os
@@ -29,6 +28,7 @@ import os
 import numpy as np
 import pytest
 
+from box_table import _Table
 from conftest import GOLDEN
 
 from gamesmanmpi_amd import Context, _lib
@@ -103,36 +103,6 @@ def _reference(root):
     assert ctx.stats()["flow_fallbacks"] == 0
     ctx.close()
     return ref
-
-
-class _Table:
-    """4 GiB of device memory from the HIP runtime the library has loaded (no second framework in
-    the test process)."""
-
-    def __init__(self):
-        _lib.lib()
-        path = [l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l][0]
-        self.hip = ctypes.CDLL(path)
-        for f, args in (("hipMalloc", [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]),
-                        ("hipMemset", [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]),
-                        ("hipFree", [ctypes.c_void_p]), ("hipDeviceSynchronize", [])):
-            getattr(self.hip, f).argtypes = args
-            getattr(self.hip, f).restype = ctypes.c_int
-        self.ptr = ctypes.c_void_p()
-        assert self.hip.hipMalloc(ctypes.byref(self.ptr), 1 << 32) == 0
-
-    def data_ptr(self):
-        return self.ptr.value
-
-    def numel(self):
-        return 1 << 32
-
-    def fill(self, byte):
-        assert self.hip.hipMemset(self.ptr, byte, 1 << 32) == 0
-        assert self.hip.hipDeviceSynchronize() == 0
-
-    def free(self):
-        assert self.hip.hipFree(self.ptr) == 0
 
 
 @pytest.fixture(scope="module")
