@@ -1229,14 +1229,18 @@ static int solve_sharded(Ctx *c, const D &desc, const key_t<D> &root) {
     }
     const uint64_t stored = gall.back();
     gall.pop_back();
-    uint64_t n = 0, tb = 0;
+    uint64_t n = 0, tb = 0, prim = 0;
     for (auto v : gall) n += v;
     for (auto &R : d->ranks)
-        for (auto &T : R.tiers) tb += T.cap * sizeof(typename KT<K>::Slot) + T.ni * (sizeof(K) + 5);
+        for (auto &T : R.tiers) {
+            tb += T.cap * sizeof(typename KT<K>::Slot) + T.ni * (sizeof(K) + 5);
+            prim += T.count - T.ni;   // stored and not listed as interior (the ranks this context runs)
+        }
     c->n_positions = n;
     c->tier_counts = gall;
     c->stats.n_positions = n;
     c->stats.n_stored = stored;
+    c->stats.n_primitive = prim;
     c->stats.n_tiers = (int32_t)d->gcount.size();
     c->stats.world = G;
     c->stats.forward_ms = t1 - t0;

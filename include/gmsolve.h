@@ -188,7 +188,8 @@ typedef struct gm_ctx gm_ctx;
 
 typedef struct {
     uint64_t n_positions;   /* reachable positions with a final record (all ranks) */
-    uint64_t n_primitive;   /* of which primitive (this rank; dense path: all) */
+    uint64_t n_primitive;   /* of which primitive (this rank; dense path: all; tier-table engines: of
+                               the stored positions, n_stored; 0 after gm_import) */
     int32_t n_tiers;        /* tiers walked */
     int32_t world;          /* ranks in the solve */
     double solve_ms;        /* wall time of the last gm_solve (host clock, device-synchronised) */
@@ -262,7 +263,16 @@ int gm_set_comm(gm_ctx *ctx, int rank, int world, const void *uid, int bytes);
  * communicator is set: every rank calls it with the same root).  Returns the
  * global number of reachable positions and the root's record (on every rank).
  * Replaces Process.run/lookup/distribute/check_for_updates/send_back/resolve
- * (src/new_process.py:37-265) and the root line of :42-53. */
+ * (src/new_process.py:37-265) and the root line of :42-53.
+ * A root that is not a position of the game is GM_E_KEY, refused before any launch.  As for a
+ * graph solve, a remoteness up to 0x3FFE always solves and one past 0x3FFF is GM_E_CAP
+ * ("remoteness exceeds 14 bits"); after a failed solve the context holds no table (gm_export &
+ * co. return GM_E_STATE) until the next solve succeeds.  Only GM_GAME_FOUR_TO_ONE comes near:
+ * one position per tier, so the root is the depth, 24575 (WIN in 0x3FFF) is the deepest root
+ * that solves and 24576 (LOSS in 0x4000) the first that does not.
+ * Known limit: the forward pass has no depth bound of its own, and every pile with |pile| <
+ * 2^60 is a valid Four-To-One root: a root far above 24576 is refused only once its whole
+ * chain of tiers has been built, or memory is gone before that. */
 int gm_solve(gm_ctx *ctx, uint64_t root_key, uint64_t *n_positions, uint16_t *root_record);
 
 /* Keys of more than 64 bits.  A board whose position string exceeds 64 bits -- GM_GAME_OTHELLO
@@ -591,7 +601,12 @@ int gm_reach(gm_ctx *ctx, const gm_reach_t *how, const uint64_t *start_words, ui
 /* Solve statistics of the last gm_solve. */
 int gm_stats(gm_ctx *ctx, gm_stats_t *out);
 
-/* Positions per tier of the last solve (this rank); *n = number of tiers. */
+/* Positions per tier of the last solve (this rank); *n = number of tiers.
+ * What counts[0] is depends on the engine.  The tier-table engines (GM_ENGINE_SPARSE,
+ * GM_ENGINE_DIST_SPARSE) count from the root's tier on: counts[i] is tier tier(root) + i, and
+ * *n is the number of tiers the solve reached.  Tic-tac-toe's one-workgroup
+ * engine (GM_ENGINE_DENSE) reports by absolute tier, the piece count: always *n = 10, counts[p]
+ * the positions with p pieces, 0 for every p below the root's. */
 int gm_tier_counts(gm_ctx *ctx, uint64_t *counts, int cap, int *n);
 
 /* Back a table with caller-owned device memory (e.g. a torch tensor's storage).

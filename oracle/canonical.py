@@ -27,6 +27,7 @@ there: ``_counter`` stays 0, ``src/new_process.py:135-162``).
 import numpy as np
 
 WIN, LOSS, TIE, DRAW, UNDECIDED = 0, 1, 2, 3, 4
+MAX_REMOTENESS = 0x3FFF   # a u16 record is (value << 14) | remoteness
 
 
 class OracleError(RuntimeError):
@@ -67,7 +68,8 @@ def solve(module, root=None, key=default_key, limit=None):
     """Strong-solve ``module`` from ``root`` (default ``initial_position()``).
 
     Returns ``(table, positions)``: ``table[key(p)] = (value, remoteness)`` and
-    ``positions[key(p)] = p`` for every reachable position ``p``.
+    ``positions[key(p)] = p`` for every reachable position ``p``.  A remoteness past
+    ``MAX_REMOTENESS`` is an OracleError, as in the C oracle.
     """
     if root is None:
         root = module.initial_position()
@@ -110,6 +112,8 @@ def solve(module, root=None, key=default_key, limit=None):
         pending = [c for c in kids if c not in table]
         if not pending:
             table[k] = fold(table[c] for c in kids)
+            if table[k][1] > MAX_REMOTENESS:   # the callers pack records: what would carry into the value
+                raise OracleError("remoteness exceeds 14 bits")
             del children_of[k]
             gray.discard(k)
             stack.pop()

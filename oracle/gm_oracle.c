@@ -490,6 +490,14 @@ static uint16_t from_pref(uint32_t best) {
     return (uint16_t)((LOSS << 14) | (low + 1));
 }
 
+/* A parent one step beyond a child at remoteness 0x3FFF has no record: 14 bits hold the
+ * remoteness, and from_pref would carry into the value bits.  The solvers refuse instead. */
+static int pref_overflows(uint32_t best) {
+    uint32_t cls = best >> 16, low = best & 0xFFFF;
+    return cls >= 2 ? low == 0 : low >= 0x3FFFu;
+}
+#define ERR_OVERFLOW "remoteness exceeds 14 bits"
+
 static int cmp_pair(const void *a, const void *b) {
     uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
     return x < y ? -1 : x > y;
@@ -550,6 +558,7 @@ int64_t oracle_solve(int game, const int32_t *params, int nparams, uint64_t root
                 uint32_t s = pref(r);
                 if (s > best) best = s;
             }
+            if (pref_overflows(best)) { snprintf(g_err, sizeof g_err, ERR_OVERFLOW); goto fail; }
             m.rec[slot] = from_pref(best);
         }
     }
@@ -979,9 +988,13 @@ int oracle_solve_layered(int game, const int32_t *params, int nparams, uint64_t 
                 const uint32_t sc = pref(lay[tc].rec[j]);
                 if (sc > best) best = sc;
             }
+            if (pref_overflows(best)) { bad |= 2; continue; }
             lay[t].rec[i] = from_pref(best);
         }
-        if (bad) { snprintf(g_err, sizeof g_err, "child missing from its tier"); err = 2; }
+        if (bad) {
+            snprintf(g_err, sizeof g_err, "%s", bad & 1 ? "child missing from its tier" : ERR_OVERFLOW);
+            err = 2;
+        }
     }
     if (err) goto done;
     {
