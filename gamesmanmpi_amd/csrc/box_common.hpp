@@ -161,4 +161,36 @@ GM_HD int bx_mirror_class45(uint32_t box, uint32_t root_box) {
     return c4 > c5 ? 1 : 2;
 }
 
+// Mirror of heaps 2 and 3 (the dataflow launches of the hybrid schedule only), the same rule on
+// the fields c2 (bits 4-5) and c3 (bits 6-7).  Heaps 2 and 3 are the digits at bits 4-5 and 6-7
+// of the row index A, so row m of swap23(C) holds the 16 bytes of row swap(m) of C
+// (bx_swap_row(BX_SWAP23, m): the two digits exchanged): the bytes unchanged, the row's address
+// moved, 16 consecutive rows (256 B) staying together.  The third class is independent of the
+// other two like them: a box is computed iff no class is 2, and stores itself and every
+// composition of its flagged swaps, up to eight boxes (bit 29 of its list entry the 2/3 flag).
+constexpr uint32_t BX_MIRROR23_FLAG = 0x20000000u;   // bit 29 of a compute-list entry
+constexpr uint32_t BX_SWAP23 = 6;                    // the transposition code of heaps (2, 3)
+GM_HD uint32_t bx_swap23(uint32_t b) {
+    const uint32_t t = ((b >> 4) ^ (b >> 6)) & 3u;
+    return b ^ (t << 4) ^ (t << 6);
+}
+GM_HD int bx_mirror_class23(uint32_t box, uint32_t root_box) {
+    const int c2 = box_coord(box, 2), c3 = box_coord(box, 3);
+    if (c2 == c3 || !box_in_region(bx_swap23(box), root_box)) return 0;
+    return c2 > c3 ? 1 : 2;
+}
+// variant v (0..7) of a compute-list entry's box: bit 0 through the 6/7 mirror, bit 1 the 4/5,
+// bit 2 the 2/3; and whether the entry's flags say that its group stores it
+GM_HD uint32_t bx_twin_box(uint32_t entry, uint32_t v) {
+    uint32_t b = entry & BX_BOX_MASK;
+    if (v & 1u) b = bx_swap67(b);
+    if (v & 2u) b = bx_swap45(b);
+    if (v & 4u) b = bx_swap23(b);
+    return b;
+}
+GM_HD bool bx_twin_stored(uint32_t entry, uint32_t v) {
+    return (!(v & 1u) || (entry & BX_MIRROR_FLAG)) && (!(v & 2u) || (entry & BX_MIRROR45_FLAG)) &&
+           (!(v & 4u) || (entry & BX_MIRROR23_FLAG));
+}
+
 }  // namespace gm

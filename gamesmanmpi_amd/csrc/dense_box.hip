@@ -43,6 +43,8 @@
 //          and of each pair that differs by the exchange of heaps 4 and 5, and store its rows
 //          again to the others (dwords 1 and 2 exchanged, bytes 1 and 2 of each dword
 //          exchanged, or both; box_common.hpp): 331,776 of the 2^20 boxes computed, all stored.
+//          The head and tail dataflow launches of the hybrid schedule add the exchange of heaps
+//          2 and 3 (the same rows at exchanged row addresses), up to eight boxes from one.
 // The max of up to 13 inputs uses v_pk_maximum3_f16: a code 0..255 in the low byte of
 // an f16 is a subnormal, ordered like the integer (the kernel keeps f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3).
@@ -72,7 +74,8 @@ typedef uint16_t bx_u16x2 __attribute__((ext_vector_type(2)));
 #define GM_BOX_MIRROR_STORE_CPOL GM_BOX_TIER_STORE_CPOL   // the mirrored boxes' rows (2 = nt)
 #endif
 #ifndef GM_BOX_MIRROR_SET
-#define GM_BOX_MIRROR_SET 3    // the mirrors GM_OPT_SYMMETRY 1 uses: bit 0 heaps 6/7, bit 1 heaps 4/5
+#define GM_BOX_MIRROR_SET 7    // the mirrors GM_OPT_SYMMETRY 1 uses: bit 0 heaps 6/7, bit 1 heaps 4/5, bit 2 heaps
+                               // 2/3 (in the hybrid schedule's dataflow launches only)
 #endif
 #ifndef GM_BOX_WAVES
 #define GM_BOX_WAVES 2         // waves per SIMD the register budget must allow
@@ -195,7 +198,7 @@ struct BxGroup {
 // (One-GPU tier launches: the list is a compute list, box_common.hpp, and box[k] keeps the
 // entry's BX_MIRROR_FLAG in bit 31.  Every use of box[k] before bx_store reads coordinate
 // fields or forms the 32-bit offset box << 12, which drop the bit, and BX_MIRROR45_FLAG in bit 30
-// with it; bx_store masks them.)
+// and BX_MIRROR23_FLAG in bit 29 with it; bx_store masks them.)
 template <bool SHARD, bool FILL = true>
 __device__ __forceinline__ BxGroup bx_group(const uint32_t *__restrict__ boxes, const uint32_t *__restrict__ fills,
                                             const uint32_t *__restrict__ srcs, const uint32_t *__restrict__ dsts,
@@ -623,11 +626,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t bx_twin_rsrc(uint8_t *table, u
 // 4/5 flag, bytes 1 and 2 of each dword exchanged, to swap45(box); with both, both permutations,
 // to swap45(swap67(box)).  No workgroup computes those boxes.  A twin whose flag is absent gets a
 // descriptor of size 0, which drops its stores (bx_twin_rsrc).
-template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI = 4, bool MIRROR = false>
+// M23 (the hybrid schedule's dataflow launches, box_flow_kernel RANGE): with the 2/3 flag (bit 29
+// of the entry) the four images above go a second time, bytes as they are, to row swap(m) (digits
+// 2 and 3 of m exchanged, bx_swap_row) of the four swap23 twins: up to eight boxes from one
+// computed.  Their words do not fit the SGPR file beside the rest: each is formed from the list
+// entry at its store.
+template <bool SHARD_, bool DIRECT = false, int CP = GM_BOX_STORE_CPOL, int NI = 4, bool MIRROR = false,
+          bool M23 = false>
 __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *p0, uint8_t *p1, uint8_t *p2,
                                          const BxGroup &G, const uint32_t *s, uint32_t lane, uint32_t i0 = 0) {
     constexpr bool SHARD = SHARD_ && !(GM_BOX_EXP & 32);
     static_assert(!(MIRROR && SHARD_), "the mirrored store is the one-GPU launches'");
+    static_assert(MIRROR || !M23, "the 2/3 mirror goes with the other two");
     __amdgpu_buffer_rsrc_t w[2];
     uint32_t tw[2][3] = {{0, 0, 0}, {0, 0, 0}};   // MIRROR: the twins of box k (bx_twin_rsrc)
 #pragma unroll
@@ -683,6 +693,31 @@ __device__ __forceinline__ void bx_store(uint8_t *table, uint8_t *msg, uint8_t *
                     if constexpr (GM_BOX_MIRROR_SET & 1)
                         __builtin_amdgcn_raw_buffer_store_b128(bx_u32x4{p[0], p[2], p[1], p[3]},
                                                                bx_twin_rsrc(table, tw[k][2]), 16u * m, 0, MC);
+                }
+            }
+        }
+        if constexpr (M23) {
+            const uint32_t m2 = bx_swap_row(BX_SWAP23, m);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                constexpr int MC = GM_BOX_MIRROR_STORE_CPOL;
+                bx_u32x4 p;
+#pragma unroll
+                for (int q = 0; q < 4; q++) p[q] = __builtin_amdgcn_perm(o[k][q], o[k][q], BX_PERM45);
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    if constexpr (!(GM_BOX_MIRROR_SET & 1))
+                        if (v & 1) continue;
+                    if constexpr (!(GM_BOX_MIRROR_SET & 2))
+                        if (v & 2) continue;
+                    // (an invalid box's entry is 0: no flags, so no twin)
+                    uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)G.box[k]);
+                    asm volatile("" : "+s"(e));   // the twin's word is formed here, not held over the rows
+                    const bool on = bx_twin_stored(e, 4u + (uint32_t)v) && !(GM_BOX_EXP & 4);
+                    const uint32_t t = (bx_twin_box(e, 4u + (uint32_t)v) << 12) | (on ? 1u : 0u);
+                    const bx_u32x4 x = (v & 2) ? p : o[k];
+                    __builtin_amdgcn_raw_buffer_store_b128((v & 1) ? bx_u32x4{x[0], x[2], x[1], x[3]} : x,
+                                                           bx_twin_rsrc(table, t), 16u * m2, 0, MC);
                 }
             }
         }
@@ -1145,17 +1180,20 @@ __device__ unsigned long long bx_ftrace[BX_FT_WORDS * BX_FT_GROUPS];
 // RANGE (the hybrid schedule's head and tail launches): the queues hold
 // the groups of a range of box-tiers of the compute list (box_common.hpp), so box[k] keeps its
 // mirror flags and a flagged box is stored two or four times, as by the tier launches
-// (bx_store MIRROR).  Every box stored gets its flag, the twins included: a parent may wait on
-// a box that no group computed.  A record with BX_FLOW_NOWAIT is of the range's first tier:
+// (bx_store MIRROR), and with the 2/3 flag (GM_BOX_MIRROR_SET bit 2; these launches' own compute
+// list, DenseBox::d_fboxes) up to eight times (bx_store M23).  Every box stored gets its flag, the
+// twins included: a parent may wait on a box that no group computed.  A record with BX_FLOW_NOWAIT is of the range's first tier:
 // its children were stored by an earlier launch of the same stream, and it does not wait.
 // (Its child rows are still read sc1, like every group's: a load policy chosen per group would
 // put the 48 loads of bx_issue into the kernel twice.)
 // The no-deadlock argument above holds for these lists as it stands: a twin's flag is set by
 // the group dequeued for its leader, and the leader is in the twin's own tier (a mirror
-// exchanges two coordinates and keeps their sum), so the group of the lowest tier still has
+// exchanges two coordinates and keeps their sum -- heaps 2/3 like 4/5 and 6/7, and so every
+// composition of them, all seven twins), so the group of the lowest tier still has
 // every child's flag coming from groups of the tier before, all of them finished or, in the
 // first tier of the range, stored by an earlier launch.
 constexpr uint32_t BX_FLOW_NOWAIT = 0x40000000u;   // bit 30 of a queue record (RANGE)
+constexpr bool BX_M23 = (GM_BOX_MIRROR_SET & 4) != 0;
 template <bool SHARD, bool RANGE = false>
 __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_flow_kernel(uint8_t *__restrict__ table,
                                                                      const uint32_t *__restrict__ boxes,
@@ -1206,21 +1244,19 @@ __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_flow_kernel(uint8_t *__r
 #if GM_BOX_FLOW_TRACE
         BX_RT(ft[3]);
 #endif
-        bx_store<false, false, GM_BOX_STORE_CPOL, 4, RANGE>(table, nullptr, nullptr, nullptr, nullptr, G, s, ln);
+        bx_store<false, false, GM_BOX_STORE_CPOL, 4, RANGE, RANGE && BX_M23>(table, nullptr, nullptr, nullptr, nullptr,
+                                                                             G, s, ln);
         BX_LDS_ORDER();
         // publish: the wave's sc1 stores done, then one lane stores each box's flag sc1
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (RANGE) {
-            // lane 4 k + v: box k itself (v = 0) or its twin under the 6/7 mirror (v & 1), the
-            // 4/5 mirror (v & 2) or both -- the boxes bx_store wrote, by the entry's flags
-            if (lane < 8u) {
-                const uint32_t e = (lane >> 2) ? G.box[1] : G.box[0], v = lane & 3u;
-                uint32_t b = e & BX_BOX_MASK;
-                if (v & 1u) b = bx_swap67(b);
-                if (v & 2u) b = bx_swap45(b);
-                const bool on = ((lane >> 2) ? G.valid[1] : G.valid[0]) && (!(v & 1u) || (e & BX_MIRROR_FLAG)) &&
-                                (!(v & 2u) || (e & BX_MIRROR45_FLAG));
-                if (on) __hip_atomic_store(&F.flag[b], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // lane 8 k + v: box k itself (v = 0) or its twin under the 6/7 mirror (v & 1), the
+            // 4/5 mirror (v & 2), the 2/3 mirror (v & 4) or their composition -- the boxes bx_store
+            // wrote, by the entry's flags
+            if (lane < 16u) {
+                const uint32_t e = (lane >> 3) ? G.box[1] : G.box[0], v = lane & 7u;
+                const bool on = ((lane >> 3) ? G.valid[1] : G.valid[0]) && bx_twin_stored(e, v);
+                if (on) __hip_atomic_store(&F.flag[bx_twin_box(e, v)], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         } else if (lane == 0) {
             __hip_atomic_store(&F.flag[G.box[0]], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1451,12 +1487,14 @@ int box_split_flow_resident(int device) {
 
 // The hybrid schedule's default tier range (GM_BOX_HYBRID, box_hybrid_wanted); 0, 40 = off.
 // Measured: the thin tiers alone, (10, 30), gain nothing over tier launches;
-// the ramp tiers pay, up to (14, 26); from (16, 24) on the thick tiers' sc1 child loads lose.
+// the ramp tiers pay.  With two mirrors the gain ended at (14, 26) (from (16, 24) on the thick
+// tiers' sc1 child loads lost); with the heap-2/3 mirror in the dataflow launches a tier costs
+// them 10/16 of the groups it costs a tier launch, and (16, 24) is the fastest of the candidates.
 #ifndef GM_BOX_HYBRID_LO
-#define GM_BOX_HYBRID_LO 14
+#define GM_BOX_HYBRID_LO 16
 #endif
 #ifndef GM_BOX_HYBRID_HI
-#define GM_BOX_HYBRID_HI 26
+#define GM_BOX_HYBRID_HI 24
 #endif
 constexpr int BOX_HYBRID_OFF_HI = 40;
 
@@ -1473,6 +1511,11 @@ struct DenseBox {
     bool mirror = false;              // GM_OPT_SYMMETRY when the lists were built
     uint32_t *d_cboxes = nullptr;
     std::vector<uint32_t> ctier_off;
+    // the hybrid schedule's dataflow launches' compute list: the heap-2/3 mirror applied as well
+    // (entries may carry BX_MIRROR23_FLAG; d_cboxes never does: the tier launches, and the re-solve
+    // after a dataflow timeout, have no 2/3 store).  d_cboxes itself where the lists are equal.
+    uint32_t *d_fboxes = nullptr;
+    std::vector<uint32_t> ftier_off;
     hipGraphExec_t graph = nullptr;
     hipStream_t graph_stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -1570,9 +1613,8 @@ static void box_flow_queues(const std::vector<uint32_t> &boxes, const std::vecto
                 for (uint32_t k = 0; k < (rec >> 31 ? 2u : 1u); k++) {
                     const uint32_t e = boxes[i + k], b = e & BX_BOX_MASK;
                     when[b] = w;
-                    if (e & BX_MIRROR_FLAG) when[bx_swap67(b)] = w;
-                    if (e & BX_MIRROR45_FLAG) when[bx_swap45(b)] = w;
-                    if ((e & BX_MIRROR_FLAG) && (e & BX_MIRROR45_FLAG)) when[bx_swap45(bx_swap67(b))] = w;
+                    for (uint32_t v = 1; v < 8; v++)   // its twins, up to seven
+                        if (bx_twin_stored(e, v)) when[bx_twin_box(e, v)] = w;
                 }
                 q[x].push_back(rec);
             }
@@ -1604,21 +1646,23 @@ static void box_region_tiers(uint32_t root_hi, std::vector<uint32_t> &boxes, std
     }
 }
 
-// The compute list of a full list (box_common.hpp bx_mirror_class67 / 45, the mirrors of
-// GM_BOX_MIRROR_SET): the boxes mirrored-to through either dropped, the order (Hilbert inside a
-// tier) kept, so the kernel's 8 XCD runs are runs of the same walk; mirror off: the full list, no
-// flags.
-void box_compute_list(uint32_t root_hi, bool mirror, const std::vector<uint32_t> &boxes,
+// The compute list of a full list (box_common.hpp bx_mirror_class67 / 45 / 23, the mirrors of
+// `set`, bits as GM_BOX_MIRROR_SET): the boxes mirrored-to through any dropped, the order (Hilbert
+// inside a tier) kept, so the kernel's 8 XCD runs are runs of the same walk; mirror off: the full
+// list, no flags.
+void box_compute_list(uint32_t root_hi, bool mirror, int set, const std::vector<uint32_t> &boxes,
                       const std::vector<uint32_t> &tier_off, std::vector<uint32_t> &cboxes,
                       std::vector<uint32_t> &ctier_off) {
     cboxes.clear();
     ctier_off.assign(1, 0);
     for (size_t t = 0; t + 1 < tier_off.size(); t++) {
         for (uint32_t i = tier_off[t]; i < tier_off[t + 1]; i++) {
-            const int c67 = (mirror && (GM_BOX_MIRROR_SET & 1)) ? bx_mirror_class67(boxes[i], root_hi) : 0;
-            const int c45 = (mirror && (GM_BOX_MIRROR_SET & 2)) ? bx_mirror_class45(boxes[i], root_hi) : 0;
-            if (c67 != 2 && c45 != 2)
-                cboxes.push_back(boxes[i] | (c67 == 1 ? BX_MIRROR_FLAG : 0u) | (c45 == 1 ? BX_MIRROR45_FLAG : 0u));
+            const int c67 = (mirror && (set & 1)) ? bx_mirror_class67(boxes[i], root_hi) : 0;
+            const int c45 = (mirror && (set & 2)) ? bx_mirror_class45(boxes[i], root_hi) : 0;
+            const int c23 = (mirror && (set & 4)) ? bx_mirror_class23(boxes[i], root_hi) : 0;
+            if (c67 != 2 && c45 != 2 && c23 != 2)
+                cboxes.push_back(boxes[i] | (c67 == 1 ? BX_MIRROR_FLAG : 0u) | (c45 == 1 ? BX_MIRROR45_FLAG : 0u) |
+                                 (c23 == 1 ? BX_MIRROR23_FLAG : 0u));
         }
         ctier_off.push_back((uint32_t)cboxes.size());
     }
@@ -1641,7 +1685,7 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     GM_HIP(hipMemcpy(d->d_boxes, d->boxes.data(), d->boxes.size() * 4, hipMemcpyHostToDevice));
     d->mirror = c->symmetry != 0;
     std::vector<uint32_t> cb;
-    box_compute_list(d->root_hi, d->mirror, d->boxes, d->tier_off, cb, d->ctier_off);
+    box_compute_list(d->root_hi, d->mirror, GM_BOX_MIRROR_SET & 3, d->boxes, d->tier_off, cb, d->ctier_off);
     GM_HIP(hipMalloc(&d->d_cboxes, std::max<size_t>(1, cb.size()) * 4));
     GM_HIP(hipMemcpy(d->d_cboxes, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
     d->flow = box_flow_wanted(c);
@@ -1658,8 +1702,16 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
         if (d->flow) {
             box_flow_queues(d->boxes, d->tier_off, 0, nt, false, d->qbase, d->qlen, qs);
         } else {
-            box_flow_queues(cb, d->ctier_off, 0, h0, true, d->hqbase[0], d->hqlen[0], qs);
-            box_flow_queues(cb, d->ctier_off, h1, nt, true, d->hqbase[1], d->hqlen[1], qs);
+            std::vector<uint32_t> fb;
+            box_compute_list(d->root_hi, d->mirror, GM_BOX_MIRROR_SET, d->boxes, d->tier_off, fb, d->ftier_off);
+            d->d_fboxes = d->d_cboxes;
+            if (fb != cb) {
+                d->d_fboxes = nullptr;
+                GM_HIP(hipMalloc(&d->d_fboxes, std::max<size_t>(1, fb.size()) * 4));
+                GM_HIP(hipMemcpy(d->d_fboxes, fb.data(), fb.size() * 4, hipMemcpyHostToDevice));
+            }
+            box_flow_queues(fb, d->ftier_off, 0, h0, true, d->hqbase[0], d->hqlen[0], qs);
+            box_flow_queues(fb, d->ftier_off, h1, nt, true, d->hqbase[1], d->hqlen[1], qs);
         }
         GM_HIP(hipMalloc(&d->d_groups, std::max<size_t>(1, qs.size()) * 4));
         GM_HIP(hipMemcpy(d->d_groups, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
@@ -1721,7 +1773,7 @@ static int box_launch_flow(Ctx *c, DenseBox *d, int range = -1) {
                            d->table, d->d_boxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
     else
         hipLaunchKernelGGL((box_flow_kernel<false, true>), dim3((uint32_t)d->hyb_grid[range]), dim3(64), d->flow_dyn,
-                           c->stream, d->table, d->d_cboxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
+                           c->stream, d->table, d->d_fboxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
     GM_HIP(hipGetLastError());
     return GM_OK;
 }
@@ -1949,7 +2001,9 @@ static void dense_box_free(Ctx *c) {
     for (auto e : d->ev)
         if (e) (void)hipEventDestroy(e);
     if (d->owned && d->table) (void)hipFree(d->table);
-    for (void *q : {(void *)d->d_boxes, (void *)d->d_cboxes, (void *)d->d_groups, (void *)d->d_flow, (void *)d->d_tables})
+    if (d->d_fboxes == d->d_cboxes) d->d_fboxes = nullptr;
+    for (void *q : {(void *)d->d_boxes, (void *)d->d_cboxes, (void *)d->d_fboxes, (void *)d->d_groups, (void *)d->d_flow,
+                    (void *)d->d_tables})
         if (q) (void)hipFree(q);
     if (d->h_res) (void)hipHostFree(d->h_res);
     delete d;

@@ -124,7 +124,10 @@ enum {
                                differ by the exchange of heaps 4 and 5, one is computed and both are
                                stored, so a computed box stores up to four (a twin's rows are the same
                                rows with dwords 1 and 2, or bytes 1 and 2 of each dword, exchanged;
-                               the build option GM_BOX_MIRROR_SET keeps one pair of heaps only); every
+                               the build option GM_BOX_MIRROR_SET keeps one pair of heaps only); the
+                               head and tail dataflow launches of the default schedule also compute one
+                               of two boxes that differ by the exchange of heaps 2 and 3 (the twin's
+                               rows are the same rows at exchanged row addresses: up to eight stored); every
                                position is still stored, so n_stored stays n_positions and gm_verify
                                checks them all.  0 = every box computed.
                                Changing it between solves rebuilds the box lists and the graph */

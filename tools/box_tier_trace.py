@@ -5,7 +5,8 @@
 
 --mirror: the groups of the compute list (GM_OPT_SYMMETRY 1), SET as GM_BOX_MIRROR_SET: 1 (the
 default of the flag alone) = of the boxes that differ by the exchange of heaps 6 and 7 only the
-one with c6 >= c7 is computed, 3 = also only c4 >= c5 of heaps 4 and 5; --last N: the last N
+one with c6 >= c7 is computed, 3 = also only c4 >= c5 of heaps 4 and 5, 7 (with --hybrid) = also
+only c2 >= c3 of heaps 2 and 3 in the dataflow launches' tiers; --last N: the last N
 solves of the trace only (the bench's timed solves, without its warm-up); --hybrid LO,HI: the
 trace is of the hybrid schedule (GM_BOX_HYBRID): box-tiers [0, LO) and (HI, 40] are one launch of
 box_flow_kernel<false, true> each, shown as one row covering its tier range (groups, time and
@@ -35,6 +36,8 @@ def tier_groups(mirror=0):
         keep &= ((b >> 14) & 7) >= ((b >> 17) & 7)
     if mirror & 2:
         keep &= ((b >> 8) & 7) >= ((b >> 11) & 7)
+    if mirror & 4:
+        keep &= ((b >> 4) & 3) >= ((b >> 6) & 3)
     t = t[keep]
     n = np.bincount(t, minlength=41)
     return (n + 1) // 2
@@ -99,7 +102,10 @@ def main():
     dur = np.array([(e - s) / 1e3 for s, e in rows]).reshape(n, per)        # us
     span = np.array([(rows[per * i + per - 1][1] - rows[per * i][0]) / 1e3 for i in range(n)])
     med = np.median(dur, axis=0)
-    g = tier_groups(a.mirror)
+    g = tier_groups(a.mirror & 3)
+    if a.mirror & 4 and a.hybrid:   # the heap-2/3 mirror: the dataflow launches' tiers only
+        flow = np.array([t < lo or t > hi for t in range(41)])
+        g = np.where(flow, tier_groups(a.mirror), g)
     if a.hybrid:
         return hybrid_report(a, segs, n, dur, span, med, g)
     thick = g >= 2 * a.round

@@ -7,14 +7,16 @@
 // Box layout: the hi bits of every dimension above the lo bits, so a halo slab of a
 // side-4 dimension is a set of whole 256-B chunks; the model counts 256-B chunks.
 //
-//   g++ -O2 -o /tmp/l2sim_box tools/l2sim_box.cpp && /tmp/l2sim_box 44442222 [K] [order] [L2 bytes] [mirror]
+//   g++ -O2 -o /tmp/l2sim_box tools/l2sim_box.cpp && /tmp/l2sim_box 44442222 [K] [order] [L2 bytes] [mirror] [lo hi]
 //
 // mirror = 1 (csrc/box_common.hpp, the one-GPU tier launches with GM_OPT_SYMMETRY 1): of each
 // pair of boxes that differ by the exchange of dimensions 6 and 7, only the box with c6 >= c7
 // is computed -- only its child reads are replayed, in the tier's order without the others --
 // and a box with c6 > c7 also writes its twin.  mirror = 2: the same on dimensions 4 and 5 as
 // well (computed: c6 >= c7 and c4 >= c5); a box writes its twin through each mirror it leads and
-// through both.
+// through both.  mirror = 3: the hybrid schedule's third mirror, dimensions 2 and 3 (computed:
+// c2 >= c3 as well), in the box-tiers outside [lo, hi] only (default 14 26: the dataflow launches'
+// tiers); a box there writes up to eight.  The halo reads of those tiers are printed on their own.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -72,6 +74,7 @@ int main(int argc, char **argv) {
     const int order = argc > 3 ? atoi(argv[3]) : 0;
     const size_t l2_bytes = argc > 4 ? atoll(argv[4]) : (4u << 20);
     const int mirror = argc > 5 ? atoi(argv[5]) : 0;
+    const int hyb_lo = argc > 7 ? atoi(argv[6]) : 14, hyb_hi = argc > 7 ? atoi(argv[7]) : 26;
     int s[8], nb[8], lb[8];
     int box_pos = 1;
     for (int i = 0; i < 8; i++) {
@@ -132,7 +135,12 @@ int main(int argc, char **argv) {
     std::vector<LRU> l2(8, LRU(l2_bytes / chunk));
     LRU mall((256u << 20) / chunk);
     uint64_t l2m = 0, mm = 0, raw = 0, peak_t = 0, ncomp = 0;
-    for (auto &t : tiers) {
+    uint64_t fl_raw = 0, fl_l2m = 0, fl_comp = 0;   // the tiers outside [lo, hi] (the dataflow launches')
+    for (size_t ti = 0; ti < tiers.size(); ti++) {
+        auto &t = tiers[ti];
+        const bool flow_tier = (int)ti < hyb_lo || (int)ti > hyb_hi;
+        const bool m23t = mirror >= 3 && flow_tier;
+        const uint64_t raw0 = raw, l2m0 = l2m;
         peak_t = std::max<uint64_t>(peak_t, t.size());
         std::stable_sort(t.begin(), t.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
         if (mirror)   // the compute list: the mirrored-to boxes dropped, the order kept
@@ -140,7 +148,7 @@ int main(int argc, char **argv) {
                                    [&](uint32_t b) {
                                        int c[8];
                                        coords(b, c);
-                                       return c[6] < c[7] || (mirror >= 2 && c[4] < c[5]);
+                                       return c[6] < c[7] || (mirror >= 2 && c[4] < c[5]) || (m23t && c[2] < c[3]);
                                    }),
                     t.end());
         ncomp += t.size();
@@ -187,18 +195,24 @@ int main(int argc, char **argv) {
                     int c[8];
                     coords(t[idx], c);
                     // the twins' rows, written by the same group: through 6/7, through 4/5, through both
-                    const bool m67 = mirror && c[6] > c[7], m45 = mirror >= 2 && c[4] > c[5];
-                    for (int tw = 1; tw < 4; tw++) {
-                        if (((tw & 1) && !m67) || ((tw & 2) && !m45)) continue;
+                    const bool m67 = mirror && c[6] > c[7], m45 = mirror >= 2 && c[4] > c[5], m23 = m23t && c[2] > c[3];
+                    for (int tw = 1; tw < 8; tw++) {
+                        if (((tw & 1) && !m67) || ((tw & 2) && !m45) || ((tw & 4) && !m23)) continue;
                         int e[8];
                         for (int i = 0; i < 8; i++) e[i] = c[i];
                         if (tw & 1) std::swap(e[6], e[7]);
                         if (tw & 2) std::swap(e[4], e[5]);
+                        if (tw & 4) std::swap(e[2], e[3]);
                         const uint64_t tb = index(e);
                         for (int qd = 0; qd < nchunks; qd++) mall.touch(tb * nchunks + qd);
                     }
                 }
             }
+        if (flow_tier) {
+            fl_raw += raw - raw0;
+            fl_l2m += l2m - l2m0;
+            fl_comp += t.size();
+        }
     }
     const double pos = 4294967296.0;
     printf("sides %s K=%d order=%d L2=%zu KiB mirror=%d: box %d pos, %llu boxes (%llu computed), %d box-tiers (peak %llu "
@@ -206,5 +220,8 @@ int main(int argc, char **argv) {
            sides_s, K, order, l2_bytes >> 10, mirror, box_pos, (unsigned long long)nbox, (unsigned long long)ncomp,
            maxt + 1, (unsigned long long)peak_t, [&] { int st = 1; for (int i = 0; i < 8; i++) st += s[i] - 1; return st; }(),
            raw * (double)chunk / pos, l2m * (double)chunk / pos, mm * (double)chunk / pos);
+    if (mirror >= 3)
+        printf("box-tiers outside [%d, %d]: %llu boxes computed, halo reads %.3f GB, L2-miss %.3f GB\n", hyb_lo, hyb_hi,
+               (unsigned long long)fl_comp, fl_raw * (double)chunk / 1e9, fl_l2m * (double)chunk / 1e9);
     return 0;
 }
