@@ -116,7 +116,8 @@ __global__ __launch_bounds__(256) void byte_digest_kernel(const uint8_t *__restr
 
 // ---------------------------------------------------------------- the readers
 // (in the unnamed namespace with the kernels they launch: every engine's translation unit has its own)
-int byte_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+int byte_query(Ctx *c, const void *keys_in, uint16_t *recs, uint64_t n) {
+    const uint64_t *keys = (const uint64_t *)keys_in;
     const ByteTables t = byte_tables_of(c);
     const auto kernel = t.box ? byte_query_kernel<1> : byte_query_kernel<0>;
     return query_keys(c, keys, recs, n, BOX_QUERY_CHUNK, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
@@ -220,9 +221,9 @@ int byte_reach(Ctx *c, const ReachReq &q) {
 }
 
 // gm_poke: one byte of the table that holds the key's unit
-int byte_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+int byte_poke(Ctx *c, const void *key, uint16_t rec) {
     const ByteTables t = byte_tables_of(c);
-    const uint64_t k = words[0];
+    const uint64_t k = *(const uint64_t *)key;
     const bool in = sub_in_region(k, c->root, t.heaps);
     const uint32_t idx = !in ? 0u : t.box ? box_index_of_key((uint32_t)k) : (uint32_t)k;
     uint8_t own = in ? 0 : 0xFF;

@@ -1832,7 +1832,8 @@ void box_tier_counts(uint64_t root, std::vector<uint64_t> &acc) {
     }
 }
 
-static int dense_box_solve(Ctx *c, uint64_t root) {
+static int dense_box_solve(Ctx *c, const void *root_key) {
+    const uint64_t root = *(const uint64_t *)root_key;
     DenseBox *d = c->dbox;
     const uint32_t rh = box_index_of_key((uint32_t)root) >> 12;
     int hlo, hhi;
@@ -1916,7 +1917,7 @@ static int dense_box_solve(Ctx *c, uint64_t root) {
         c->box_flow_failed = true;
         c->box_flow_fallbacks++;
         const int fb = c->box_flow_fallbacks;
-        const int rc = dense_box_solve(c, root);
+        const int rc = dense_box_solve(c, root_key);
         c->stats.flow_fallbacks = fb;
         return rc;
     }
@@ -1971,7 +1972,8 @@ void box_region_keys(uint64_t root, uint64_t *keys, uint64_t n) {
 }
 
 // Export: the root's region in ascending key order.
-static int dense_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dense_box_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     DenseBox *d = c->dbox;
     *n = c->n_positions;
     if (!keys) return GM_OK;

@@ -1057,7 +1057,8 @@ static int dense_sub_ensure(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-static int dense_sub_solve(Ctx *c, uint64_t root) {
+static int dense_sub_solve(Ctx *c, const void *root_key) {
+    const uint64_t root = *(const uint64_t *)root_key;
     GM_TRY(dense_sub_ensure(c, root));
     DenseSub *d = c->dsub;
 #ifdef GM_WK_TRACE
@@ -1148,7 +1149,8 @@ static int dense_sub_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-static int dense_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dense_sub_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     DenseSub *d = c->dsub;
     *n = c->n_positions;
     if (!keys) return GM_OK;

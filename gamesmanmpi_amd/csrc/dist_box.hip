@@ -1280,7 +1280,8 @@ static int bx_launch(Ctx *c, DistBox *d, bool op_events) {
     return GM_OK;
 }
 
-static int dist_box_solve(Ctx *c, uint64_t root) {
+static int dist_box_solve(Ctx *c, const void *root_key) {
+    const uint64_t root = *(const uint64_t *)root_key;
     const bool loopback = c->world <= 1 && c->virtual_ranks > 1;
     const int G = loopback ? c->virtual_ranks : c->world;
     const bool ipc = !loopback && c->box_transport == 1;
@@ -1439,7 +1440,8 @@ static void dist_box_bytes(Ctx *c, ByteTables *t) {
 
 // Export: every virtual rank together = the root's region; a rank of a multi-process solve:
 // the positions of the boxes it computed, ascending.
-static int dist_box_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dist_box_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     DistBox *d = c->dist_box;
     if (d->loopback) {
         *n = c->n_positions;

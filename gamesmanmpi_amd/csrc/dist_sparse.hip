@@ -1259,121 +1259,27 @@ static int finish_solve(Ctx *c, int rc) {
     return rc;
 }
 
-static int dist_sparse_solve(Ctx *c, uint64_t root) {
-    if (c->wide) { set_error("this game's keys are 128-bit: gm_solve_key"); return GM_E_ARG; }
-    return finish_solve(c, with_desc(c, [&](const auto &desc) { return solve_sharded(c, desc, root); }));
+static int dist_sparse_solve(Ctx *c, const void *root) {
+    return finish_solve(c, with_desc_wide(c, [&](const auto &desc) {
+        return solve_sharded(c, desc, *(const key_t<std::decay_t<decltype(desc)>> *)root);
+    }));
 }
 
-int dist_sparse_solve_wide(Ctx *c, const K128 &root) {
-    if (!c->wide) { set_error("not a 128-bit-key game"); return GM_E_ARG; }
-    return finish_solve(c, solve_sharded(c, c->oth8, root));
-}
-
-// the tier tables of every rank this context runs (its hash share in a multi-process solve)
-template <class K>
-static TierList<K> rank_tiers(Ctx *c) {
-    TierList<K> l;
-    for (auto &R : static_cast<DistSparseK<K> *>(c->dist_sp)->ranks)
-        for (auto &T : R.tiers) l.push_back(&T);
-    return l;
-}
-
-template <class D>
-static int export_ranks(Ctx *c, const D &desc, key_t<D> *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    const int rc = tiers_export(c, desc, rank_tiers<key_t<D>>(c), keys, recs, cap, n);
-    if (rc == GM_E_CAP) set_error("export buffer too small");
-    return rc;
-}
-
-static int dist_sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    if (c->wide) { set_error("this game's keys are 128-bit: gm_export_key"); return GM_E_ARG; }
-    return with_desc(c, [&](const auto &desc) { return export_ranks(c, desc, keys, recs, cap, n); });
-}
-
-int dist_sparse_export_wide(Ctx *c, K128 *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    if (!c->wide) { set_error("not a 128-bit-key game"); return GM_E_ARG; }
-    return export_ranks(c, c->oth8, keys, recs, cap, n);
-}
-
-static int dist_sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        return tiers_digest(c, desc, rank_tiers<key_t<std::decay_t<decltype(desc)>>>(c), digest, n);
-    });
-}
-
-static int dist_sparse_histogram(Ctx *c, Hist *out) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        using K = key_t<std::decay_t<decltype(desc)>>;
-        size_t depth = 0;
-        for (auto &R : static_cast<DistSparseK<K> *>(c->dist_sp)->ranks) depth = std::max(depth, R.tiers.size());
-        return tiers_histogram(c, desc, rank_tiers<K>(c), depth, out);
-    });
-}
-
-static int dist_sparse_select(Ctx *c, const SelectDev &s) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        return tiers_select(c, desc, rank_tiers<key_t<std::decay_t<decltype(desc)>>>(c), s);
-    });
-}
-
-// a key is stored by its owner rank: one group of tables per rank
-template <class D>
-static int query_ranks(Ctx *c, const D &desc, const key_t<D> *keys, uint16_t *recs, uint64_t n) {
-    using K = key_t<D>;
-    auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
-    std::vector<TierGroup<K>> groups;
-    for (auto &R : d->ranks) groups.push_back({&R.tiers, d->t_root});
-    return tiers_query(c, desc, groups, keys, recs, n);
-}
-
-static int dist_sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    if (!n) return GM_OK;
-    if (c->wide) { set_error("this game's keys are 128-bit: gm_query_key"); return GM_E_ARG; }
-    return with_desc(c, [&](const auto &desc) { return query_ranks(c, desc, keys, recs, n); });
-}
-
-int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n) {
-    if (!n) return GM_OK;
-    if (!c->wide) { set_error("not a 128-bit-key game"); return GM_E_ARG; }
-    return query_ranks(c, c->oth8, keys, recs, n);
-}
-
-// gm_verify / gm_poke over every virtual rank's tables (one group per owner rank, in rank order);
-// a rank of a multi-process solve holds one group of G and is refused in gm_api.hip
-template <class K>
-static std::vector<TierGroup<K>> rank_groups(Ctx *c) {
-    auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
-    std::vector<TierGroup<K>> groups;
-    for (auto &R : d->ranks) groups.push_back({&R.tiers, d->t_root});
-    return groups;
-}
-
-static int dist_sparse_verify(Ctx *c, const VerifyDev &v) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        return tiers_verify(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), v);
-    });
-}
-
-static int dist_sparse_moves(Ctx *c, const MovesReq &r) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        return tiers_moves(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), r);
-    });
-}
-
-static int dist_sparse_reach(Ctx *c, const ReachReq &q) {
-    return with_desc_wide(c, [&](const auto &desc) {
-        return tiers_reach(c, desc, rank_groups<key_t<std::decay_t<decltype(desc)>>>(c), q);
-    });
-}
-
-static int dist_sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    if (c->wide) {
-        K128 k;
-        if (!DescOthello8::from_words(words, &k)) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
-        return tiers_poke(c, c->oth8, rank_groups<K128>(c), k, rec);
+// how the shared read entries (sparse_tables.hpp TierReads) find this engine's tables: a key is
+// stored by its owner rank, so one group per rank this context runs, in rank order
+struct RankTabs {
+    template <class F>
+    static int desc(Ctx *c, F &&f) { return with_desc_wide(c, f); }
+    template <class K>
+    static std::vector<TierGroup<K>> groups(Ctx *c) {
+        auto *d = static_cast<DistSparseK<K> *>(c->dist_sp);
+        std::vector<TierGroup<K>> groups;
+        for (auto &R : d->ranks) groups.push_back({&R.tiers, d->t_root});
+        return groups;
     }
-    return with_desc(c, [&](const auto &desc) { return tiers_poke(c, desc, rank_groups<uint64_t>(c), words[0], rec); });
-}
+};
+template struct TierReads<RankTabs>;
+using RankReads = TierReads<RankTabs>;
 
 template <class K>
 static void free_ranks(Ctx *c, DistSparseK<K> *d) {
@@ -1427,9 +1333,8 @@ static int dist_sparse_import(Ctx *c, const void *keys, const uint16_t *recs, ui
     return GM_OK;
 }
 
-GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, dist_sparse_export,
-                 dist_sparse_query, dist_sparse_digest, dist_sparse_histogram, dist_sparse_select, nullptr, dist_sparse_free,
-                 dist_sparse_verify, dist_sparse_poke, dist_sparse_import, dist_sparse_moves, nullptr,
-                 dist_sparse_reach)
+GM_ENGINE_RECORD(dist_sparse_engine, GM_ENGINE_DIST_SPARSE, dist_sparse_solve, RankReads::export_, RankReads::query,
+                 RankReads::digest, RankReads::histogram, RankReads::select, nullptr, dist_sparse_free,
+                 RankReads::verify, RankReads::poke, dist_sparse_import, RankReads::moves, nullptr, RankReads::reach)
 
 }  // namespace gm

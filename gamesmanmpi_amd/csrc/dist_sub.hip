@@ -658,7 +658,8 @@ static int run_solve(Ctx *c, DistSub *d) {
 
 static void dist_sub_free(Ctx *c);
 
-static int dist_sub_solve(Ctx *c, uint64_t root) {
+static int dist_sub_solve(Ctx *c, const void *root_key) {
+    const uint64_t root = *(const uint64_t *)root_key;
     const bool loopback = c->virtual_ranks > 1;
     const int G = loopback ? c->virtual_ranks : c->world;
     DistSub *d = c->dist_sub;
@@ -729,7 +730,8 @@ static void dist_sub_bytes(Ctx *c, ByteTables *t) {
     for (auto &R : d->ranks) t->parts.push_back({R.table, R.dlist, R.off.back()});
 }
 
-static int dist_sub_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int dist_sub_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     DistSub *d = c->dist_sub;
     hipStream_t H = c->stream;
     const uint64_t bsz = 1ull << (4 * d->low);

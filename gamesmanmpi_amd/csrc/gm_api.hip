@@ -118,7 +118,8 @@ void dev_free(Ctx *c, void *p) {
 // forces the hash-sharded engine, e.g. over a one-rank communicator.
 static const Engine *choose_engine(const Ctx *c, bool sharded) {
     const bool dense_game = c->game == GM_GAME_SUBTRACT || c->game == GM_GAME_TTT;
-    if (c->engine_opt == GM_ENGINE_DIST_SPARSE) return &dist_sparse_engine;
+    // forced, or a wide game: the one engine that stores wide keys
+    if (c->engine_opt == GM_ENGINE_DIST_SPARSE || c->wide) return &dist_sparse_engine;
     if (c->engine_opt == GM_ENGINE_SPARSE || !dense_game) return sharded ? &dist_sparse_engine : &sparse_engine;
     if (c->game == GM_GAME_TTT) return sharded ? &dist_sparse_engine : &small_dense_engine;
     // the 8-heap game on the box engine splits in dist_box.hip; other heap counts and
@@ -129,6 +130,74 @@ static const Engine *choose_engine(const Ctx *c, bool sharded) {
 
 static bool key_valid(const Ctx *c, uint64_t k) {
     return with_desc(c, [&](const auto &d) { return (int)d.valid(k); }) > 0;
+}
+
+// ---------------------------------------------------------------- keys across the ABI
+// The ABI speaks key words (gm_key_words() per key), the engines the context's device key type
+// (gm_internal.hpp Engine).  The codec of a multi-word game is named here and nowhere below:
+// Othello 8x8, whose 144-bit position string is three words and whose device key is a K128.
+static int key_words(const Ctx *c) { return c->wide ? 3 : 1; }
+static size_t key_bytes(const Ctx *c) { return c->wide ? sizeof(K128) : 8; }
+static bool key_from_words(const Ctx *, const uint64_t *w, void *key) { return DescOthello8::from_words(w, (K128 *)key); }
+static void key_to_words(const Ctx *, const void *key, uint64_t *w) { DescOthello8::to_words(*(const K128 *)key, w); }
+
+static int refuse_wide(const Ctx *c, const char *call) {
+    if (c->wide) { set_error("this game's keys have %d words: %s_key", key_words(c), call); return GM_E_ARG; }
+    return GM_OK;
+}
+
+// what device_keys makes of words that are no position
+enum class BadKey {
+    Fails,     // GM_E_KEY, the error names the key's index
+    Unsolved,  // the all-zero key, which no table holds; the index goes to DeviceKeys::bad (record 0xFFFF)
+    Skipped    // the all-zero key, which the engines' moves and reach pass over
+};
+struct DeviceKeys {
+    const void *p = nullptr;            // n keys of the context's device key type
+    std::vector<unsigned char> held;    // ... held here on a wide context; a one-word context's are the caller's words
+    std::vector<uint64_t> bad;
+};
+// ABI words to device keys.  A one-word context's words are its keys: no copy, and whether a key
+// is a position is the engine's affair
+static int device_keys(const Ctx *c, const uint64_t *words, uint64_t n, BadKey bad, const char *what, DeviceKeys *out) {
+    out->p = words;
+    if (!c->wide) return GM_OK;
+    const size_t KB = key_bytes(c), W = key_words(c);
+    out->held.assign(n * KB, 0);
+    out->p = out->held.data();
+    for (uint64_t i = 0; i < n; i++) {
+        if (key_from_words(c, words + W * i, &out->held[i * KB])) continue;
+        memset(&out->held[i * KB], 0, KB);
+        if (bad == BadKey::Unsolved) out->bad.push_back(i);
+        if (bad != BadKey::Fails) continue;
+        std::string hex;
+        char one[24];
+        for (size_t j = 0; j < W; j++) { snprintf(one, sizeof one, " 0x%llx", (unsigned long long)words[W * i + j]); hex += one; }
+        set_error("%s%s (index %llu) is not a valid position", what, hex.c_str(), (unsigned long long)i);
+        return GM_E_KEY;
+    }
+    return GM_OK;
+}
+
+// Device keys to ABI words in ascending ABI order (a multi-word key: the position string as one
+// integer, its last word the most significant).  Returns the permutation -- words of row i are
+// those of keys[perm[i]] -- so that a caller can carry records and sides along.
+static std::vector<uint64_t> abi_sorted(const Ctx *c, const void *keys, uint64_t n, uint64_t *words) {
+    const size_t KB = key_bytes(c), W = key_words(c);
+    std::vector<uint64_t> w(c->wide ? W * n : 0), perm(n);
+    for (uint64_t i = 0; i < n; i++) {
+        perm[i] = i;
+        if (c->wide) key_to_words(c, (const unsigned char *)keys + i * KB, &w[W * i]);
+    }
+    const uint64_t *src = c->wide ? w.data() : (const uint64_t *)keys;
+    std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) {
+        for (size_t j = W; j-- > 0;)
+            if (src[W * a + j] != src[W * b + j]) return src[W * a + j] < src[W * b + j];
+        return false;
+    });
+    for (uint64_t i = 0; i < n; i++)
+        for (size_t j = 0; j < W; j++) words[W * i + j] = src[W * perm[i] + j];
+    return perm;
 }
 
 // keys per chunk of gm_moves: GM_MOVES_CHUNK (a development variable, as GM_SPARSE_BATCH) lets a
@@ -357,6 +426,95 @@ static void free_engines(Ctx *c) {
         e->free_(c);
 }
 
+// ---------------------------------------------------------------- around a solve or an import
+// A root from ABI words: GM_E_KEY unless it is a position.  Checked before solve_begin, so that
+// a refused root leaves the context's table alone (gm_solve) ...
+struct Root {
+    uint64_t one = 0;
+    DeviceKeys wide;
+};
+static int parse_root(const Ctx *c, const uint64_t *words, const char *call, Root *r) {
+    if (c->wide) return device_keys(c, words, 1, BadKey::Fails, call, &r->wide);
+    if (!key_valid(c, words[0])) {
+        set_error("%s 0x%llx is not a valid position", call, (unsigned long long)words[0]);
+        return GM_E_KEY;
+    }
+    r->one = words[0];
+    return GM_OK;
+}
+// ... and made the context's after it, with the symmetry reduction of a solve from it (games.hpp):
+// Toot-and-Otto's mirror when the root is its own mirror image, Othello's board symmetries that
+// fix the root (DescOthello::sym)
+static void set_root(Ctx *c, const Root &r) {
+    c->root = r.one;
+    if (c->wide) memcpy(&c->root_wide, r.wide.p, sizeof c->root_wide);
+    if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(c->root) == c->root) ? 1u : 0u;
+    if (c->game == GM_GAME_OTHELLO && !c->wide) c->oth.sym = c->symmetry ? c->oth.stabilizer(c->root) : 0u;
+}
+
+// From here on the context no longer holds a table, so a failure leaves it unsolved; the stats
+// are the coming solve's.  keep_launches: gm_solve under GM_OPT_TIMING accumulates them
+static void solve_begin(Ctx *c, int world, bool keep_launches) {
+    c->solved = false;
+    c->solved_by = nullptr;
+    c->hist_is_kept = false;
+    c->n_draw = 0;
+    const int32_t launches = keep_launches ? c->stats.kernel_launches : 0;
+    c->stats = gm_stats_t{};
+    c->stats.kernel_launches = launches;
+    c->stats.world = world;
+}
+
+static int solve_finish(Ctx *c, const Engine *e, int world, uint64_t *n_positions, uint16_t *root_record) {
+    if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;   // engines without a symmetry reduction
+    c->stats.engine = e->id;
+    c->stats.world = world;
+    c->solved = true;
+    c->solved_by = e;
+    if (n_positions) *n_positions = c->n_positions;
+    if (root_record) *root_record = c->root_record;
+    return GM_OK;
+}
+
+// The communicator of a solve by engine e.  Virtual ranks run inside the context and need none.
+// Otherwise two rules say whether the solve has ranks to connect:
+//   one-word keys   `sharded`: more than one process, or GM_ENGINE_DIST_SPARSE forced (e.g. over
+//                   a one-rank communicator); such a solve insists on a unique id
+//   wide keys       the hash-sharded engine is the only engine, so one process without a unique
+//                   id is simply G = 1; ranks are connected when there are several or an id was set
+// A transport that needs no communicator (the split box engine's IPC stores, the sparse engine's
+// IPC pulls; both also run with the ranks sharing one GPU, where RCCL refuses) still needs the
+// unique id: it names the rendezvous.
+static int solve_comm(Ctx *c, const Engine *e, bool sharded) {
+    if (c->world > 1 && c->virtual_ranks > 1) {
+        set_error("virtual ranks and a multi-process communicator are exclusive");
+        return GM_E_ARG;
+    }
+    if (c->virtual_ranks > 1) return GM_OK;
+    const bool ranks = c->wide ? (c->world > 1 || c->have_uid) : sharded;
+    if (!ranks) return GM_OK;
+    const bool no_comm = e == &dist_box_engine ? c->box_transport == 1
+                                               : (e == &dist_sparse_engine && c->sparse_transport == 1);
+    if (!c->have_uid) {
+        if (no_comm) set_error("the IPC transport needs gm_set_comm with a unique id (it names the rendezvous)");
+        else set_error("a %d-rank solve of this game needs an RCCL communicator (gm_set_comm with a unique id)", c->world);
+        return GM_E_COMM;
+    }
+    return no_comm ? (int)GM_OK : ensure_comm(c);
+}
+
+// each dense SUBTRACT engine holds (or adopts) a whole table: choosing one releases the other two's
+static void release_other_dense(Ctx *c, const Engine *e) {
+    if (e == &dense_box_engine || e == &dist_box_engine || e == &dense_sub_engine)
+        for (const Engine *o : {&dense_sub_engine, &dense_box_engine, &dist_box_engine})
+            if (o != e) o->free_(c);
+}
+
+static int need_device(const Ctx *c) {
+    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
+    return GM_OK;
+}
+
 }  // namespace gm
 
 using namespace gm;
@@ -534,7 +692,7 @@ int gm_set_option(gm_ctx *h, int opt, int64_t v) {
 int gm_pack_initial(gm_ctx *h, uint64_t *key) {
     if (!h || !key) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (c->wide) { set_error("this game's keys have %d words: gm_pack_initial_key", gm_key_words(h)); return GM_E_ARG; }
+    GM_TRY(refuse_wide(c, "gm_pack_initial"));
     switch (c->game) {
     case GM_GAME_FOUR_TO_ONE: *key = 4; return GM_OK;   // four_to_one.py:8-10
     case GM_GAME_TTT: *key = 0; return GM_OK;           // empty board
@@ -556,7 +714,7 @@ int gm_pack_initial(gm_ctx *h, uint64_t *key) {
 int gm_expand_host(gm_ctx *h, uint64_t key, uint64_t *children, int cap, int *n, int *prim, int64_t *tier) {
     if (!h || !n || !prim || !tier) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (c->wide) { set_error("this game's keys have %d words: gm_expand_host_key", gm_key_words(h)); return GM_E_ARG; }
+    GM_TRY(refuse_wide(c, "gm_expand_host"));
     uint64_t kids[32];
     int p = UNDECIDED, k = 0;
     int64_t t = 0;
@@ -626,67 +784,14 @@ int gm_set_comm(gm_ctx *h, int rank, int world, const void *uid, int bytes) {
 
 int gm_solve(gm_ctx *h, uint64_t root, uint64_t *n_positions, uint16_t *root_record) {
     if (!h) return GM_E_ARG;
-    Ctx *c = &h->c;
-    if (c->wide) { set_error("this game's keys have %d words: gm_solve_key", gm_key_words(h)); return GM_E_ARG; }
-    if (c->game == GM_GAME_GRAPH) { set_error("a GM_GAME_GRAPH context is solved with gm_solve_graph"); return GM_E_GAME; }
-    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
-    if (!key_valid(c, root)) { set_error("root key 0x%llx is not a valid position", (unsigned long long)root); return GM_E_KEY; }
-    GM_HIP(hipSetDevice(c->device));
-    c->solved = false;
-    c->solved_by = nullptr;
-    c->hist_is_kept = false;
-    c->n_draw = 0;
-    int32_t launches = c->stats.kernel_launches;
-    c->stats = gm_stats_t{};
-    c->stats.kernel_launches = c->timing ? launches : 0;
-    c->stats.world = c->world;
-    c->root = root;
-    // symmetry reduction (games.hpp): Toot-and-Otto's mirror, when the root is its own mirror image;
-    if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(root) == root) ? 1u : 0u;
-    // Othello: the board symmetries that fix the root (games.hpp DescOthello::sym)
-    if (c->game == GM_GAME_OTHELLO) c->oth.sym = c->symmetry ? c->oth.stabilizer(root) : 0u;
-    const bool sharded = c->world > 1 || c->virtual_ranks > 1 || c->engine_opt == GM_ENGINE_DIST_SPARSE;
-    if (sharded && c->world > 1 && c->virtual_ranks > 1) {
-        set_error("virtual ranks and a multi-process communicator are exclusive");
-        return GM_E_ARG;
-    }
-    const Engine *e = choose_engine(c, sharded);
-    // transports that need no communicator: the split box engine's IPC stores and the sparse
-    // engine's IPC pulls (both also run with the ranks sharing one GPU, where RCCL refuses)
-    const bool no_comm = e == &dist_box_engine ? c->box_transport == 1
-                                               : (e == &dist_sparse_engine && c->sparse_transport == 1);
-    if (sharded && c->virtual_ranks <= 1 && no_comm && !c->have_uid) {
-        set_error("the IPC transport needs gm_set_comm with a unique id (it names the rendezvous)");
-        return GM_E_COMM;
-    }
-    if (sharded && c->virtual_ranks <= 1 && !no_comm) {
-        if (!c->have_uid) {
-            set_error("a %d-rank solve of this game needs an RCCL communicator (gm_set_comm with a unique id)", c->world);
-            return GM_E_COMM;
-        }
-        GM_TRY(ensure_comm(c));
-    }
-    // each dense SUBTRACT engine holds (or adopts) a whole table: choosing one releases the other two's
-    if (e == &dense_box_engine || e == &dist_box_engine || e == &dense_sub_engine)
-        for (const Engine *o : {&dense_sub_engine, &dense_box_engine, &dist_box_engine})
-            if (o != e) o->free_(c);
-    GM_TRY(e->solve(c, root));
-    if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;   // engines without a symmetry reduction
-    c->stats.engine = e->id;
-    c->stats.world = sharded ? (c->world > 1 ? c->world : c->virtual_ranks) : 1;
-    c->solved = true;
-    c->solved_by = e;
-    if (n_positions) *n_positions = c->n_positions;
-    if (root_record) *root_record = c->root_record;
-    return GM_OK;
+    GM_TRY(refuse_wide(&h->c, "gm_solve"));
+    return gm_solve_key(h, &root, n_positions, root_record);
 }
 
 // ---------------------------------------------------------------- multi-word keys
-static constexpr int WIDE_WORDS = 3;   // Othello 8x8: the 144-bit position string (games.hpp DescOthello8)
-
 int gm_key_words(gm_ctx *h) {
     if (!h) return GM_E_ARG;
-    return h->c.wide ? WIDE_WORDS : 1;
+    return key_words(&h->c);
 }
 
 int gm_pack_initial_key(gm_ctx *h, uint64_t *words) {
@@ -729,76 +834,45 @@ int gm_expand_host_key(gm_ctx *h, const uint64_t *words, uint64_t *children, int
     }
     if (*n > cap) { set_error("children buffer holds %d, need %d", cap, *n); return GM_E_CAP; }
     if (children)
-        for (int i = 0; i < *n; i++) DescOthello8::to_words(kids[i], children + (size_t)WIDE_WORDS * i);
+        for (int i = 0; i < *n; i++) DescOthello8::to_words(kids[i], children + (size_t)key_words(c) * i);
     return GM_OK;
 }
 
 int gm_solve_key(gm_ctx *h, const uint64_t *words, uint64_t *n_positions, uint16_t *root_record) {
     if (!h || !words) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (!c->wide) return gm_solve(h, words[0], n_positions, root_record);
-    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
-    K128 root;
-    if (!DescOthello8::from_words(words, &root)) {
-        set_error("root key is not a valid position (an 8x8 Othello position keeps its four centre squares)");
-        return GM_E_KEY;
-    }
+    if (c->game == GM_GAME_GRAPH) { set_error("a GM_GAME_GRAPH context is solved with gm_solve_graph"); return GM_E_GAME; }
+    GM_TRY(need_device(c));
+    Root root;
+    GM_TRY(parse_root(c, words, "gm_solve: root key", &root));
     GM_HIP(hipSetDevice(c->device));
-    c->solved = false;
-    c->solved_by = nullptr;
-    c->hist_is_kept = false;
-    c->n_draw = 0;
-    c->stats = gm_stats_t{};
-    if (c->world > 1 && c->virtual_ranks > 1) {
-        set_error("virtual ranks and a multi-process communicator are exclusive");
-        return GM_E_ARG;
-    }
-    // the hash-sharded sparse engine is this game's engine: one GPU (G = 1), virtual ranks, or
-    // one process per rank over RCCL / the IPC transport
-    if (c->virtual_ranks <= 1 && (c->world > 1 || c->have_uid)) {
-        if (!c->have_uid) { set_error("a %d-rank solve needs gm_set_comm with a unique id", c->world); return GM_E_COMM; }
-        if (c->sparse_transport != 1) GM_TRY(ensure_comm(c));
-    }
-    c->root_wide = root;
-    GM_TRY(dist_sparse_solve_wide(c, root));
-    if (!c->stats.n_stored) c->stats.n_stored = c->stats.n_positions;
-    c->stats.engine = GM_ENGINE_DIST_SPARSE;
-    c->stats.world = c->world > 1 ? c->world : std::max(1, c->virtual_ranks);
-    c->solved = true;
-    c->solved_by = &dist_sparse_engine;   // digest and histogram go the common way
-    if (n_positions) *n_positions = c->n_positions;
-    if (root_record) *root_record = c->root_record;
-    return GM_OK;
+    solve_begin(c, c->world, c->timing && !c->wide);
+    set_root(c, root);
+    // a wide game's engine is the hash-sharded sparse engine: one GPU (G = 1), virtual ranks, or
+    // one process per rank
+    const bool sharded = c->wide || c->world > 1 || c->virtual_ranks > 1 || c->engine_opt == GM_ENGINE_DIST_SPARSE;
+    const Engine *e = choose_engine(c, sharded);
+    GM_TRY(solve_comm(c, e, sharded));
+    release_other_dense(c, e);
+    GM_TRY(e->solve(c, c->root_key()));
+    return solve_finish(c, e, !sharded ? 1 : c->world > 1 ? c->world : c->virtual_ranks, n_positions, root_record);
 }
 
 int gm_export_key(gm_ctx *h, uint64_t *words, uint16_t *recs, uint64_t cap, uint64_t *n) {
     GM_TRY(need_solved(h));
     if (!n || (words && !recs)) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (!c->wide) return gm_export(h, words, recs, cap, n);
     GM_HIP(hipSetDevice(c->device));
-    GM_TRY(dist_sparse_export_wide(c, nullptr, nullptr, 0, n));
+    // the engine's order is the device keys': a one-word context's are the ABI's
+    if (!c->wide) return c->solved_by->export_(c, words, recs, cap, n);
+    GM_TRY(c->solved_by->export_(c, nullptr, nullptr, 0, n));
     if (!words) return GM_OK;
     if (cap < *n) { set_error("export buffer too small"); return GM_E_CAP; }
-    std::vector<K128> k(*n);
+    std::vector<unsigned char> k(*n * key_bytes(c));
     std::vector<uint16_t> r(*n);
-    GM_TRY(dist_sparse_export_wide(c, k.data(), r.data(), *n, n));
-    std::vector<uint64_t> w((size_t)WIDE_WORDS * *n);
-    for (uint64_t i = 0; i < *n; i++) DescOthello8::to_words(k[i], &w[(size_t)WIDE_WORDS * i]);
-    // sorted by the key's integer value (most significant word first)
-    std::vector<uint64_t> idx(*n);
-    for (uint64_t i = 0; i < *n; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-        for (int j = WIDE_WORDS - 1; j >= 0; j--) {
-            const uint64_t x = w[(size_t)WIDE_WORDS * a + j], y = w[(size_t)WIDE_WORDS * b + j];
-            if (x != y) return x < y;
-        }
-        return false;
-    });
-    for (uint64_t i = 0; i < *n; i++) {
-        for (int j = 0; j < WIDE_WORDS; j++) words[(size_t)WIDE_WORDS * i + j] = w[(size_t)WIDE_WORDS * idx[i] + j];
-        recs[i] = r[idx[i]];
-    }
+    GM_TRY(c->solved_by->export_(c, k.data(), r.data(), *n, n));
+    const std::vector<uint64_t> perm = abi_sorted(c, k.data(), *n, words);
+    for (uint64_t i = 0; i < *n; i++) recs[i] = r[perm[i]];
     return GM_OK;
 }
 
@@ -806,17 +880,11 @@ int gm_query_key(gm_ctx *h, const uint64_t *words, uint16_t *recs, uint64_t n) {
     GM_TRY(need_solved(h));
     if (n && (!words || !recs)) return GM_E_ARG;
     Ctx *c = &h->c;
-    if (!c->wide) return gm_query(h, words, recs, n);
     GM_HIP(hipSetDevice(c->device));
-    std::vector<K128> k(n);
-    std::vector<uint8_t> ok(n);
-    for (uint64_t i = 0; i < n; i++) {
-        ok[i] = DescOthello8::from_words(words + (size_t)WIDE_WORDS * i, &k[i]);
-        if (!ok[i]) k[i] = K128{0, 0};   // no valid key: answers 0xFFFF below
-    }
-    GM_TRY(dist_sparse_query_wide(c, k.data(), recs, n));
-    for (uint64_t i = 0; i < n; i++)
-        if (!ok[i]) recs[i] = REC_UNSOLVED;
+    DeviceKeys k;
+    GM_TRY(device_keys(c, words, n, BadKey::Unsolved, "gm_query_key: key", &k));
+    GM_TRY(c->solved_by->query(c, k.p, recs, n));
+    for (uint64_t i : k.bad) recs[i] = REC_UNSOLVED;
     return GM_OK;
 }
 
@@ -825,26 +893,16 @@ int gm_solve_graph(gm_ctx *h, uint64_t n, const uint8_t *prim, const uint64_t *o
     if (!h) return GM_E_ARG;
     Ctx *c = &h->c;
     if (c->game != GM_GAME_GRAPH) { set_error("gm_solve_graph needs a GM_GAME_GRAPH context"); return GM_E_GAME; }
-    // from here on a failure leaves the context without a table: the one it held is not this graph's
-    c->solved = false;
-    c->solved_by = nullptr;
-    c->hist_is_kept = false;
-    c->n_draw = 0;
+    solve_begin(c, 1, false);   // the table the context held is not this graph's
     if (!prim || !off) { set_error("gm_solve_graph needs primitive and child_off"); return GM_E_ARG; }
-    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
+    GM_TRY(need_device(c));
     if (n >= (1ull << 32)) { set_error("graphs are limited to 2^32 - 1 positions"); return GM_E_ARG; }
     for (uint64_t i = 0; i < n; i++)
         if (off[i + 1] < off[i]) { set_error("child_off is not monotone at %llu", (unsigned long long)i); return GM_E_ARG; }
     if (off[n] && !kid) { set_error("gm_solve_graph needs child_idx"); return GM_E_ARG; }
     GM_HIP(hipSetDevice(c->device));
-    c->stats = gm_stats_t{};
-    c->stats.world = 1;
     GM_TRY(graph_solve(c, n, prim, off, kid));
-    c->stats.engine = GM_ENGINE_GRAPH;
-    c->solved = true;
-    c->solved_by = &graph_engine;
-    if (root_record) *root_record = c->root_record;
-    return GM_OK;
+    return solve_finish(c, &graph_engine, 1, nullptr, root_record);
 }
 
 static int need_solved(gm_ctx *h) {
@@ -857,18 +915,14 @@ int gm_import(gm_ctx *h, const uint64_t *root_words, const uint64_t *key_words, 
               uint64_t *n_positions, uint16_t *root_record) {
     if (!h) return GM_E_ARG;
     Ctx *c = &h->c;
-    // from here on a refusal leaves the context without a table, as a failed solve does
-    c->solved = false;
-    c->solved_by = nullptr;
-    c->hist_is_kept = false;
-    c->n_draw = 0;
+    solve_begin(c, 1, false);   // a refusal leaves the context without a table, as a failed solve does
     if (!root_words || !key_words || !records) { set_error("gm_import: root_words, key_words or records is NULL"); return GM_E_ARG; }
     if (!n) { set_error("gm_import: n is 0"); return GM_E_ARG; }
     if (c->game == GM_GAME_GRAPH) {
         set_error("gm_import: the keys of a GM_GAME_GRAPH table are the host walk's numbering, which a table does not carry");
         return GM_E_GAME;
     }
-    if (c->device < 0) { set_error("no HIP device is visible: the solver needs an MI355X (gfx950)"); return GM_E_HIP; }
+    GM_TRY(need_device(c));
     if (c->world > 1 || c->virtual_ranks > 1) {
         set_error("gm_import builds the whole table in one context: not for rank %d of %d processes or %d virtual ranks",
                   c->rank, c->world, c->virtual_ranks);
@@ -878,83 +932,50 @@ int gm_import(gm_ctx *h, const uint64_t *root_words, const uint64_t *key_words, 
         set_error("gm_import: GM_ENGINE_DIST_SPARSE on a one-word context; the one-GPU engines import its tables");
         return GM_E_ARG;
     }
-    const Engine *e = c->wide ? &dist_sparse_engine : choose_engine(c, false);
+    const Engine *e = choose_engine(c, false);
     if (e == &dense_box_engine) {
         set_error("gm_import: the box engine's tables are not imported; set GM_OPT_SUB_INTERLEAVE 10 for the block engine");
         return GM_E_GAME;
     }
     if (!e->import_) { set_error("gm_import: this engine's tables are not imported"); return GM_E_GAME; }
-    K128 root_wide{0, 0};
-    if (c->wide) {
-        if (!DescOthello8::from_words(root_words, &root_wide)) {
-            set_error("root key is not a valid position (an 8x8 Othello position keeps its four centre squares)");
-            return GM_E_KEY;
-        }
-    } else if (!key_valid(c, root_words[0])) {
-        set_error("root key 0x%llx is not a valid position", (unsigned long long)root_words[0]);
-        return GM_E_KEY;
-    }
+    Root root;
+    GM_TRY(parse_root(c, root_words, "gm_import: root key", &root));
     GM_HIP(hipSetDevice(c->device));
-    c->stats = gm_stats_t{};
-    c->stats.world = 1;
-    c->root = c->wide ? 0 : root_words[0];
-    c->root_wide = root_wide;
-    // the symmetry reduction of a solve from this root (gm_solve)
-    if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(c->root) == c->root) ? 1u : 0u;
-    if (c->game == GM_GAME_OTHELLO && !c->wide) c->oth.sym = c->symmetry ? c->oth.stabilizer(c->root) : 0u;
-    if (e == &dense_sub_engine)
-        for (const Engine *o : {&dense_box_engine, &dist_box_engine}) o->free_(c);
-    std::vector<K128> wide_keys;
-    if (c->wide) {
-        wide_keys.resize(n);
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t *w = key_words + (size_t)WIDE_WORDS * i;
-            if (!DescOthello8::from_words(w, &wide_keys[i])) {
-                set_error("gm_import: key 0x%llx 0x%llx 0x%llx (index %llu) is not a valid position", (unsigned long long)w[0],
-                          (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)i);
-                return GM_E_KEY;
-            }
-        }
-    }
+    set_root(c, root);
+    release_other_dense(c, e);
+    DeviceKeys keys;
+    GM_TRY(device_keys(c, key_words, n, BadKey::Fails, "gm_import: key", &keys));
     const double t0 = now_ms();
-    const int rc = e->import_(c, c->wide ? (const void *)wide_keys.data() : (const void *)key_words, records, n);
+    const int rc = e->import_(c, keys.p, records, n);
     if (rc != GM_OK) {
         e->free_(c);
         return rc;
     }
     c->stats.solve_ms = now_ms() - t0;
-    c->stats.engine = e->id;
     // the stored record of the root, 0xFFFF when the table does not hold it (gm_verify: root_ok = 0)
     // (read as every other read is, through solved_by: the byte-table readers take their view from it)
     uint16_t rr = REC_UNSOLVED;
     c->solved_by = e;
-    const int rq = c->wide ? dist_sparse_query_wide(c, &c->root_wide, &rr, 1) : e->query(c, &c->root, &rr, 1);
+    const int rq = e->query(c, c->root_key(), &rr, 1);
     if (rq != GM_OK) {
         c->solved_by = nullptr;
         e->free_(c);
         return rq;
     }
     c->root_record = rr;
-    c->solved = true;
-    if (n_positions) *n_positions = c->n_positions;
-    if (root_record) *root_record = c->root_record;
-    return GM_OK;
+    return solve_finish(c, e, 1, n_positions, root_record);
 }
 
 int gm_export(gm_ctx *h, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
     GM_TRY(need_solved(h));
-    if (!n || (keys && !recs)) return GM_E_ARG;
-    Ctx *c = &h->c;
-    GM_HIP(hipSetDevice(c->device));
-    return c->solved_by->export_(c, keys, recs, cap, n);
+    GM_TRY(refuse_wide(&h->c, "gm_export"));
+    return gm_export_key(h, keys, recs, cap, n);
 }
 
 int gm_query(gm_ctx *h, const uint64_t *keys, uint16_t *recs, uint64_t n) {
     GM_TRY(need_solved(h));
-    if (n && (!keys || !recs)) return GM_E_ARG;
-    Ctx *c = &h->c;
-    GM_HIP(hipSetDevice(c->device));
-    return c->solved_by->query(c, keys, recs, n);
+    GM_TRY(refuse_wide(&h->c, "gm_query"));
+    return gm_query_key(h, keys, recs, n);
 }
 
 int gm_digest(gm_ctx *h, uint64_t *digest, uint64_t *n) {
@@ -1011,7 +1032,6 @@ int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap
     GM_TRY(need_whole_table(c, "gm_verify"));
     GM_HIP(hipSetDevice(c->device));
     const uint64_t want = bad_key_words ? cap : 0;
-    const uint64_t key_bytes = c->wide ? sizeof(K128) : 8;
     gm_verify_t r{};
     std::vector<unsigned char> raw;
     uint64_t nb = 0;
@@ -1019,7 +1039,7 @@ int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap
     // has room for them, is checked again into a list of the right size
     for (uint64_t dev_cap = std::min(want, VF_FIRST_CAP);;) {
         VerifyRun run;
-        GM_TRY(verify_begin(c, dev_cap, key_bytes, &run));
+        GM_TRY(verify_begin(c, dev_cap, key_bytes(c), &run));
         const int rc = c->solved_by->verify(c, run.dev);
         const int rc2 = verify_end(c, &run, &r, &raw);
         if (rc != GM_OK) return rc;
@@ -1030,31 +1050,12 @@ int gm_verify(gm_ctx *h, gm_verify_t *out, uint64_t *bad_key_words, uint64_t cap
     }
     // the root: stored, with the record the solve returned
     uint16_t rr = REC_UNSOLVED;
-    if (c->wide) GM_TRY(dist_sparse_query_wide(c, &c->root_wide, &rr, 1));
-    else GM_TRY(c->solved_by->query(c, &c->root, &rr, 1));
+    GM_TRY(c->solved_by->query(c, c->root_key(), &rr, 1));
     r.root_ok = rr != REC_UNSOLVED && rr == c->root_record;
     *out = r;
     if (n_bad) *n_bad = nb;
     if (!want) return GM_OK;
-    // ascending ABI key order (a wide key: the position string as one integer)
-    const int W = c->wide ? WIDE_WORDS : 1;
-    const uint64_t n = raw.size() / key_bytes;
-    std::vector<uint64_t> w((size_t)W * n);
-    for (uint64_t i = 0; i < n; i++) {
-        if (c->wide) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
-        else w[i] = ((const uint64_t *)raw.data())[i];
-    }
-    std::vector<uint64_t> idx(n);
-    for (uint64_t i = 0; i < n; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-        for (int j = W - 1; j >= 0; j--) {
-            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
-            if (x != y) return x < y;
-        }
-        return false;
-    });
-    for (uint64_t i = 0; i < n; i++)
-        for (int j = 0; j < W; j++) bad_key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
+    abi_sorted(c, raw.data(), raw.size() / key_bytes(c), bad_key_words);
     return GM_OK;
 }
 
@@ -1068,7 +1069,6 @@ int gm_select(gm_ctx *h, const gm_select_t *what, uint64_t *key_words, uint16_t 
     if (!c->solved_by->select) { set_error("gm_select: this engine's tables are not selected from"); return GM_E_STATE; }
     GM_HIP(hipSetDevice(c->device));
     const uint64_t want = key_words ? cap : 0;
-    const uint64_t key_bytes = c->wide ? sizeof(K128) : 8;
     std::vector<unsigned char> raw;
     std::vector<uint16_t> rr;
     uint64_t found = 0;
@@ -1076,7 +1076,7 @@ int gm_select(gm_ctx *h, const gm_select_t *what, uint64_t *key_words, uint16_t 
     // them, the table is read again into a list of exactly that room
     for (uint64_t dev_cap = std::min(want, SEL_FIRST_CAP);;) {
         SelectRun run;
-        GM_TRY(select_begin(c, *what, dev_cap, key_bytes, &run));
+        GM_TRY(select_begin(c, *what, dev_cap, key_bytes(c), &run));
         const int rc = c->solved_by->select(c, run.dev);
         const int rc2 = select_end(c, &run, &found, &raw, &rr);
         if (rc != GM_OK) return rc;
@@ -1086,34 +1086,9 @@ int gm_select(gm_ctx *h, const gm_select_t *what, uint64_t *key_words, uint16_t 
     }
     *n = found;
     if (!want) return GM_OK;
-    const uint64_t m = rr.size();
-    if (!c->wide) {
-        std::vector<std::pair<uint64_t, uint16_t>> out(m);
-        for (uint64_t i = 0; i < m; i++) out[i] = {((const uint64_t *)raw.data())[i], rr[i]};
-        std::sort(out.begin(), out.end());
-        for (uint64_t i = 0; i < m; i++) {
-            key_words[i] = out[i].first;
-            if (records) records[i] = out[i].second;
-        }
-        return GM_OK;
-    }
-    // ascending ABI key order (a wide key: the position string as one integer)
-    const int W = WIDE_WORDS;
-    std::vector<uint64_t> w((size_t)W * m);
-    for (uint64_t i = 0; i < m; i++) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
-    std::vector<uint64_t> idx(m);
-    for (uint64_t i = 0; i < m; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-        for (int j = W - 1; j >= 0; j--) {
-            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
-            if (x != y) return x < y;
-        }
-        return false;
-    });
-    for (uint64_t i = 0; i < m; i++) {
-        for (int j = 0; j < W; j++) key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
-        if (records) records[i] = rr[idx[i]];
-    }
+    const std::vector<uint64_t> perm = abi_sorted(c, raw.data(), rr.size(), key_words);
+    if (records)
+        for (size_t i = 0; i < perm.size(); i++) records[i] = rr[perm[i]];
     return GM_OK;
 }
 
@@ -1128,17 +1103,9 @@ int gm_moves(gm_ctx *h, const uint64_t *key_words, uint64_t n, gm_moves_t *heads
     *n_children = 0;
     if (!n) return GM_OK;
     GM_HIP(hipSetDevice(c->device));
-    MovesReq r{key_words, 8, 1, n, heads, child_words, child_records, cap, n_children};
-    std::vector<K128> wide_keys;
-    if (c->wide) {
-        wide_keys.resize(n);
-        for (uint64_t i = 0; i < n; i++)
-            if (!DescOthello8::from_words(key_words + (size_t)WIDE_WORDS * i, &wide_keys[i]))
-                wide_keys[i] = K128{0, 0};   // no valid key: record 0xFFFF, no children
-        r.keys = wide_keys.data();
-        r.key_bytes = sizeof(K128);
-        r.words = WIDE_WORDS;
-    }
+    DeviceKeys k;   // words that are no position: record 0xFFFF, no children
+    GM_TRY(device_keys(c, key_words, n, BadKey::Skipped, "gm_moves: key", &k));
+    const MovesReq r{k.p, key_bytes(c), gm::key_words(c), n, heads, child_words, child_records, cap, n_children};
     return c->solved_by->moves(c, r);
 }
 
@@ -1159,16 +1126,9 @@ int gm_reach(gm_ctx *h, const gm_reach_t *how, const uint64_t *start_words, uint
     std::vector<uint8_t> ss;
     if (n_starts) {
         GM_HIP(hipSetDevice(c->device));
-        ReachReq q{*how, start_words, 8, n_starts, key_words ? cap : 0, out, &pc, &raw, &rr, &ss};
-        std::vector<K128> wide_keys;
-        if (c->wide) {
-            wide_keys.resize(n_starts);
-            for (uint64_t i = 0; i < n_starts; i++)
-                if (!DescOthello8::from_words(start_words + (size_t)WIDE_WORDS * i, &wide_keys[i]))
-                    wide_keys[i] = K128{0, 0};   // no valid key: skipped
-            q.starts = wide_keys.data();
-            q.key_bytes = sizeof(K128);
-        }
+        DeviceKeys k;
+        GM_TRY(device_keys(c, start_words, n_starts, BadKey::Skipped, "gm_reach: start", &k));
+        const ReachReq q{*how, k.p, key_bytes(c), n_starts, key_words ? cap : 0, out, &pc, &raw, &rr, &ss};
         GM_TRY(c->solved_by->reach(c, q));
     }
     if (ply_counts && ply_cap > 0) {
@@ -1178,28 +1138,11 @@ int gm_reach(gm_ctx *h, const gm_reach_t *how, const uint64_t *start_words, uint
         }
         for (int d = 0; d < ply_cap; d++) ply_counts[d] = (size_t)d < pc.size() ? pc[d] : 0;
     }
-    // ascending ABI key order (a wide key: the position string as one integer)
-    const uint64_t m = rr.size();
-    if (!m) return GM_OK;
-    const int W = c->wide ? WIDE_WORDS : 1;
-    std::vector<uint64_t> w((size_t)W * m);
-    for (uint64_t i = 0; i < m; i++) {
-        if (c->wide) DescOthello8::to_words(((const K128 *)raw.data())[i], &w[(size_t)W * i]);
-        else w[i] = ((const uint64_t *)raw.data())[i];
-    }
-    std::vector<uint64_t> idx(m);
-    for (uint64_t i = 0; i < m; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-        for (int j = W - 1; j >= 0; j--) {
-            const uint64_t x = w[(size_t)W * a + j], y = w[(size_t)W * b + j];
-            if (x != y) return x < y;
-        }
-        return false;
-    });
-    for (uint64_t i = 0; i < m; i++) {
-        for (int j = 0; j < W; j++) key_words[(size_t)W * i + j] = w[(size_t)W * idx[i] + j];
-        if (records) records[i] = rr[idx[i]];
-        if (sides) sides[i] = ss[idx[i]];
+    if (rr.empty()) return GM_OK;
+    const std::vector<uint64_t> perm = abi_sorted(c, raw.data(), rr.size(), key_words);
+    for (size_t i = 0; i < perm.size(); i++) {
+        if (records) records[i] = rr[perm[i]];
+        if (sides) sides[i] = ss[perm[i]];
     }
     return GM_OK;
 }
@@ -1214,7 +1157,9 @@ int gm_poke(gm_ctx *h, const uint64_t *key_words, uint16_t record) {
     GM_TRY(need_whole_table(c, "gm_poke"));
     GM_HIP(hipSetDevice(c->device));
     c->hist_is_kept = false;
-    return c->solved_by->poke(c, key_words, record);
+    DeviceKeys k;
+    GM_TRY(device_keys(c, key_words, 1, BadKey::Fails, "gm_poke: key", &k));
+    return c->solved_by->poke(c, k.p, record);
 }
 
 int gm_draw_count(gm_ctx *h, uint64_t *n_draw) {

@@ -120,7 +120,9 @@ struct Ctx {
     bool solved = false;
     const Engine *solved_by = nullptr;   // the engine whose table the context holds (set with solved)
     uint64_t root = 0;
-    K128 root_wide{0, 0};    // a wide context's root (gm_solve_key), for gm_verify's root check
+    K128 root_wide{0, 0};    // a wide context's root (gm_solve_key, gm_import)
+    // the root as Engine's entries take keys
+    const void *root_key() const { return wide ? (const void *)&root_wide : (const void *)&root; }
     uint64_t n_positions = 0;
     uint16_t root_record = REC_UNSOLVED;
     uint64_t n_draw = 0;     // DRAW positions of the last solve (gm_draw_count): a loopy graph solve's, else 0
@@ -149,24 +151,29 @@ struct Ctx {
 };
 
 // One engine's entry points (each returns GM_OK or a GM_E_* code).  Every engine defines one
-// record next to its functions; gm_solve picks one per solve from the context's options
-// (gm_api.hip choose_engine), the solve entry points store it in Ctx::solved_by, and every read
-// of the solved table (export, query, digest, histogram, select, verify, moves, reach, dense table, rank stats) goes through it.
+// record next to its functions; the solve entry points pick one from the context's options
+// (gm_api.hip choose_engine) and store it in Ctx::solved_by, and every read of the solved table
+// (export, query, digest, histogram, select, verify, moves, reach, poke, dense table, rank stats)
+// goes through it.  Keys cross the record in the context's device key type -- uint64_t, or K128
+// when Ctx::wide -- behind void pointers: gm_api.hip converts ABI words on the way in
+// (device_keys) and orders and converts them on the way out (abi_sorted), an engine that stores
+// one-word keys casts at the top of its entry, and the hash-sharded sparse engine, the one that
+// also stores K128, dispatches on the descriptor (with_desc_wide).
 struct Engine {
     int id;                                            // GM_ENGINE_*, reported as gm_stats_t.engine
-    int (*solve)(Ctx *c, uint64_t root);               // null: the graph engine (graph_solve)
-    int (*export_)(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-    int (*query)(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
+    int (*solve)(Ctx *c, const void *root);            // null: the graph engine (graph_solve)
+    int (*export_)(Ctx *c, void *keys, uint16_t *recs, uint64_t cap, uint64_t *n);   // ascending device keys
+    int (*query)(Ctx *c, const void *keys, uint16_t *recs, uint64_t n);
     int (*digest)(Ctx *c, uint64_t *digest, uint64_t *n);
     int (*histogram)(Ctx *c, Hist *out);
     int (*select)(Ctx *c, const SelectDev &s);         // gm_select: every matching position into the accumulator
     int (*table)(Ctx *c, void **p, uint64_t *bytes);   // null: the engine has no dense table
     void (*free_)(Ctx *c);
     int (*verify)(Ctx *c, const VerifyDev &v);         // gm_verify: every stored position into the accumulator
-    int (*poke)(Ctx *c, const uint64_t *words, uint16_t rec);   // gm_poke: one stored record overwritten (test hook)
-    // gm_import: the table of root c->root (c->root_wide) built from n (key, record) pairs; keys are
-    // uint64_t, or K128 on a wide context.  Sets n_positions, tier_counts and the table's share of
-    // stats; on failure the caller frees the engine.  null: the engine's tables cannot be imported
+    int (*poke)(Ctx *c, const void *key, uint16_t rec);   // gm_poke: one stored record overwritten (test hook)
+    // gm_import: the table of root c->root (c->root_wide) built from n (key, record) pairs.  Sets
+    // n_positions, tier_counts and the table's share of stats; on failure the caller frees the
+    // engine.  null: the engine's tables cannot be imported
     int (*import_)(Ctx *c, const void *keys, const uint16_t *recs, uint64_t n);
     // gm_moves: every key's record, children (the plugin's gen_moves order), their records and
     // the mover's choice into the request's arrays (moves_common.hpp)
@@ -238,10 +245,6 @@ int dist_sub_plan(int heaps, int world, int rank, const int32_t *opts, int what,
                   uint64_t off_cap, uint64_t *n_off, uint32_t *data, uint64_t data_cap, uint64_t *n_data);
 int dist_sparse_layout(int G, int S, const uint64_t *mat, int r, uint64_t *seg, uint64_t *send_off,
                        uint64_t *recv_off, uint64_t *recv_seg);
-// 128-bit keys (gm_*_key) do not fit the record: the hash-sharded sparse engine's wide entry points
-int dist_sparse_solve_wide(Ctx *c, const K128 &root);
-int dist_sparse_export_wide(Ctx *c, K128 *keys, uint16_t *recs, uint64_t cap, uint64_t *n);
-int dist_sparse_query_wide(Ctx *c, const K128 *keys, uint16_t *recs, uint64_t n);
 int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, const uint32_t *kid);
 
 double now_ms();

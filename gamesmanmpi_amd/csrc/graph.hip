@@ -162,7 +162,8 @@ int graph_solve(Ctx *c, uint64_t n, const uint8_t *prim, const uint64_t *off, co
     return GM_OK;
 }
 
-static int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int graph_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     Graph *g = c->graph;
     *n = g->n;
     if (!keys) return GM_OK;
@@ -177,7 +178,8 @@ static int graph_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, ui
     return GM_OK;
 }
 
-static int graph_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int graph_query(Ctx *c, const void *keys_in, uint16_t *recs, uint64_t n) {
+    const uint64_t *keys = (const uint64_t *)keys_in;
     Graph *g = c->graph;
     return query_keys(c, keys, recs, n, n, [&](const uint64_t *dk, uint16_t *dr, uint64_t m) {
         hipLaunchKernelGGL(graph_records_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, g->score, dk,
@@ -385,12 +387,13 @@ static int graph_reach(Ctx *c, const ReachReq &q) {
         });
 }
 
-static int graph_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+static int graph_poke(Ctx *c, const void *key, uint16_t rec) {
     Graph *g = c->graph;
-    if (words[0] >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
+    const uint64_t k = *(const uint64_t *)key;
+    if (k >= g->n) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
     if (rec == REC_DRAW && !g->loopy) { set_error("gm_poke: not a record"); return GM_E_ARG; }
     const uint16_t s = graph_score(rec);
-    GM_HIP(hipMemcpyAsync(g->score + words[0], &s, 2, hipMemcpyHostToDevice, c->stream));
+    GM_HIP(hipMemcpyAsync(g->score + k, &s, 2, hipMemcpyHostToDevice, c->stream));
     GM_HIP(hipStreamSynchronize(c->stream));
     return GM_OK;
 }

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(1024) void small_dense_kernel(D d, uint64_t root, i
     if (tid == 0) { info[0] = s_err; info[1] = s_cnt; info[2] = s_prim; }
 }
 
-static int small_dense_solve(Ctx *c, uint64_t root) {
+static int small_dense_solve(Ctx *c, const void *root_key) {
+    const uint64_t root = *(const uint64_t *)root_key;
     if (c->game != GM_GAME_TTT) { set_error("small dense engine supports tic-tac-toe only"); return GM_E_GAME; }
     SmallDense *s = c->sd;
     if (!s) {
@@ -117,7 +118,8 @@ static int small_dense_solve(Ctx *c, uint64_t root) {
     return GM_OK;
 }
 
-static int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+static int small_dense_export(Ctx *c, void *keys_out, uint16_t *recs, uint64_t cap, uint64_t *n) {
+    uint64_t *keys = (uint64_t *)keys_out;
     SmallDense *s = c->sd;
     *n = c->n_positions;
     if (!keys) return GM_OK;
@@ -128,7 +130,8 @@ static int small_dense_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t c
     return GM_OK;
 }
 
-static int small_dense_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
+static int small_dense_query(Ctx *c, const void *keys_in, uint16_t *recs, uint64_t n) {
+    const uint64_t *keys = (const uint64_t *)keys_in;
     SmallDense *s = c->sd;
     for (uint64_t i = 0; i < n; i++) recs[i] = keys[i] < s->slots ? s->h_rec[keys[i]] : REC_UNSOLVED;
     return GM_OK;
@@ -222,9 +225,9 @@ static int small_dense_verify(Ctx *c, const VerifyDev &v) {
 }
 
 // the device table and the host copy gm_query answers from
-static int small_dense_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
+static int small_dense_poke(Ctx *c, const void *key, uint16_t rec) {
     SmallDense *s = c->sd;
-    const uint64_t k = words[0];
+    const uint64_t k = *(const uint64_t *)key;
     if (k >= s->slots || s->h_rec[k] == REC_UNSOLVED) { set_error("gm_poke: the key is not a stored position"); return GM_E_KEY; }
     s->h_rec[k] = rec;
     GM_HIP(hipMemcpyAsync(s->d_rec + k, &s->h_rec[k], 2, hipMemcpyHostToDevice, c->stream));

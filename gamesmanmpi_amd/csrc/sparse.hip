@@ -657,7 +657,6 @@ static int probe_stats(Ctx *c, Sparse *sp) {
 }
 
 static void sparse_free(Ctx *c);
-static int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n);
 
 template <class D>
 static int solve_with(Ctx *c, const D &d, uint64_t root) {
@@ -782,7 +781,7 @@ static int solve_with(Ctx *c, const D &d, uint64_t root) {
     {
         uint64_t rk[1] = {root};
         uint16_t rr[1];
-        GM_TRY(sparse_query(c, rk, rr, 1));
+        GM_TRY(tiers_query(c, d, {TierGroup<uint64_t>{&sp->tiers, sp->t_root}}, rk, rr, 1));
         c->root_record = rr[0];
     }
     uint64_t n = 0, tb = 0, stored = 0, prim = 0;
@@ -816,63 +815,19 @@ static int solve_with(Ctx *c, const D &d, uint64_t root) {
     return GM_OK;
 }
 
-static int sparse_solve(Ctx *c, uint64_t root) {
-    return with_desc(c, [&](const auto &d) { return solve_with(c, d, root); });
+static int sparse_solve(Ctx *c, const void *root) {
+    return with_desc(c, [&](const auto &d) { return solve_with(c, d, *(const uint64_t *)root); });
 }
 
-static TierList<uint64_t> tier_list(const Sparse *sp) {
-    TierList<uint64_t> l;
-    for (auto &T : sp->tiers) l.push_back(&T);
-    return l;
-}
-
-static int sparse_query(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_query(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, keys, recs, n);
-    });
-}
-
-static int sparse_export(Ctx *c, uint64_t *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
-    return with_desc(c, [&](const auto &d) { return tiers_export(c, d, tier_list(c->sp), keys, recs, cap, n); });
-}
-
-static int sparse_digest(Ctx *c, uint64_t *digest, uint64_t *n) {
-    return with_desc(c, [&](const auto &d) { return tiers_digest(c, d, tier_list(c->sp), digest, n); });
-}
-
-static int sparse_histogram(Ctx *c, Hist *out) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_histogram(c, d, tier_list(c->sp), c->sp->tiers.size(), out);
-    });
-}
-
-static int sparse_select(Ctx *c, const SelectDev &s) {
-    return with_desc(c, [&](const auto &d) { return tiers_select(c, d, tier_list(c->sp), s); });
-}
-
-static int sparse_verify(Ctx *c, const VerifyDev &v) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_verify(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, v);
-    });
-}
-
-static int sparse_moves(Ctx *c, const MovesReq &r) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_moves(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, r);
-    });
-}
-
-static int sparse_reach(Ctx *c, const ReachReq &q) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_reach(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, q);
-    });
-}
-
-static int sparse_poke(Ctx *c, const uint64_t *words, uint16_t rec) {
-    return with_desc(c, [&](const auto &d) {
-        return tiers_poke(c, d, {TierGroup<uint64_t>{&c->sp->tiers, c->sp->t_root}}, words[0], rec);
-    });
-}
+// how the shared read entries (sparse_tables.hpp TierReads) find this engine's tables: one group
+struct SparseTabs {
+    template <class F>
+    static int desc(Ctx *c, F &&f) { return with_desc(c, f); }
+    template <class K>
+    static std::vector<TierGroup<K>> groups(Ctx *c) { return {{&c->sp->tiers, c->sp->t_root}}; }
+};
+template struct TierReads<SparseTabs>;
+using SparseReads = TierReads<SparseTabs>;
 
 static void sparse_free(Ctx *c) {
     Sparse *sp = c->sp;
@@ -903,8 +858,8 @@ static int sparse_import(Ctx *c, const void *keys, const uint16_t *recs, uint64_
     });
 }
 
-GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, sparse_export,
-                 sparse_query, sparse_digest, sparse_histogram, sparse_select, nullptr, sparse_free, sparse_verify, sparse_poke,
-                 sparse_import, sparse_moves, nullptr, sparse_reach)
+GM_ENGINE_RECORD(sparse_engine, GM_ENGINE_SPARSE, sparse_solve, SparseReads::export_, SparseReads::query,
+                 SparseReads::digest, SparseReads::histogram, SparseReads::select, nullptr, sparse_free,
+                 SparseReads::verify, SparseReads::poke, sparse_import, SparseReads::moves, nullptr, SparseReads::reach)
 
 }  // namespace gm

@@ -1027,6 +1027,69 @@ inline int tiers_poke(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>>
     return GM_OK;
 }
 
+// ----------------------------------------------------------------- record entries
+// The nine read entries of an engine record (gm_internal.hpp Engine) over tier tables, once for
+// both sparse engines.  E says how an engine names its tables:
+//   E::desc(c, f)      f with the context's descriptor (with_desc, or with_desc_wide)
+//   E::groups<K>(c)    its groups of tier tables: one, or one per rank it runs (a rank of a
+//                      multi-process solve holds its hash share; gm_api.hip refuses it the reads
+//                      that need the whole table)
+// A translation unit instantiates TierReads<E> explicitly, so that its device pass, which sees
+// no record (GM_ENGINE_RECORD), emits the kernels too.
+template <class D>
+struct TierView {
+    using K = key_t<D>;
+    const D &d;
+    std::vector<TierGroup<K>> groups;
+    TierList<K> tiers;   // every tier of every group
+    size_t depth = 0;    // the most tiers a group holds
+    static K *keys(void *p) { return (K *)p; }   // the record's keys: K is the context's device key type
+    static const K *keys(const void *p) { return (const K *)p; }
+};
+
+template <class E>
+struct TierReads {
+    template <class F>
+    static int with_tables(Ctx *c, F &&f) {
+        return E::desc(c, [&](const auto &d) {
+            using D = std::decay_t<decltype(d)>;
+            TierView<D> v{d, E::template groups<key_t<D>>(c), {}, 0};
+            for (auto &g : v.groups) {
+                v.depth = std::max(v.depth, g.tiers->size());
+                for (auto &T : *g.tiers) v.tiers.push_back(&T);
+            }
+            return f(v);
+        });
+    }
+    static int export_(Ctx *c, void *keys, uint16_t *recs, uint64_t cap, uint64_t *n) {
+        return with_tables(c, [&](const auto &v) { return tiers_export(c, v.d, v.tiers, v.keys(keys), recs, cap, n); });
+    }
+    static int query(Ctx *c, const void *keys, uint16_t *recs, uint64_t n) {
+        return with_tables(c, [&](const auto &v) { return tiers_query(c, v.d, v.groups, v.keys(keys), recs, n); });
+    }
+    static int digest(Ctx *c, uint64_t *digest, uint64_t *n) {
+        return with_tables(c, [&](const auto &v) { return tiers_digest(c, v.d, v.tiers, digest, n); });
+    }
+    static int histogram(Ctx *c, Hist *out) {
+        return with_tables(c, [&](const auto &v) { return tiers_histogram(c, v.d, v.tiers, v.depth, out); });
+    }
+    static int select(Ctx *c, const SelectDev &s) {
+        return with_tables(c, [&](const auto &v) { return tiers_select(c, v.d, v.tiers, s); });
+    }
+    static int verify(Ctx *c, const VerifyDev &vf) {
+        return with_tables(c, [&](const auto &v) { return tiers_verify(c, v.d, v.groups, vf); });
+    }
+    static int moves(Ctx *c, const MovesReq &r) {
+        return with_tables(c, [&](const auto &v) { return tiers_moves(c, v.d, v.groups, r); });
+    }
+    static int reach(Ctx *c, const ReachReq &q) {
+        return with_tables(c, [&](const auto &v) { return tiers_reach(c, v.d, v.groups, q); });
+    }
+    static int poke(Ctx *c, const void *key, uint16_t rec) {
+        return with_tables(c, [&](const auto &v) { return tiers_poke(c, v.d, v.groups, *v.keys(key), rec); });
+    }
+};
+
 // ------------------------------------------------------------------ import
 // gm_import: the tier tables a solve from the root would hold had it produced exactly the given
 // (key, record) pairs -- what the readers above look at, built without a solve.  Four passes

@@ -75,8 +75,17 @@ class Context:
         self.game_id = game_id
         self.params = tuple(params)
         # u64 words per key: 1, or 3 for boards past 64 bits (Othello 8x8); keys are then Python
-        # ints on the host and (n, words) uint64 arrays in bulk (gm_*_key)
+        # ints on the host and (n, words) uint64 arrays in bulk.  Every call goes through the
+        # gm_*_key forms, which equal the one-word forms on a one-word game
         self.words = self.L.gm_key_words(h)
+
+    def _words(self, key):
+        """One key (a Python int) as the words array the gm_*_key calls take."""
+        return (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
+
+    def _keys(self, a):
+        """An (n, words) array the library filled, as callers get it: 1-D for one-word keys."""
+        return a if self.words > 1 else a[:, 0]
 
     def set_option(self, opt, value):
         _lib.check(self.L.gm_set_option(self.h, opt, int(value)))
@@ -89,22 +98,14 @@ class Context:
         _lib.check(self.L.gm_set_comm(self.h, rank, world, buf, 128 if buf is not None else 0))
 
     def initial(self):
-        if self.words > 1:
-            w = (ctypes.c_uint64 * self.words)()
-            _lib.check(self.L.gm_pack_initial_key(self.h, w))
-            return _lib.words_to_int(w)
-        k = ctypes.c_uint64()
-        _lib.check(self.L.gm_pack_initial(self.h, ctypes.byref(k)))
-        return k.value
+        w = (ctypes.c_uint64 * self.words)()
+        _lib.check(self.L.gm_pack_initial_key(self.h, w))
+        return _lib.words_to_int(w)
 
     def solve(self, root):
         n = ctypes.c_uint64()
         r = ctypes.c_uint16()
-        if self.words > 1:
-            w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(root, self.words))
-            _lib.check(self.L.gm_solve_key(self.h, w, ctypes.byref(n), ctypes.byref(r)))
-        else:
-            _lib.check(self.L.gm_solve(self.h, root, ctypes.byref(n), ctypes.byref(r)))
+        _lib.check(self.L.gm_solve_key(self.h, self._words(root), ctypes.byref(n), ctypes.byref(r)))
         return n.value, r.value
 
     def import_table(self, keys, records, root):
@@ -115,10 +116,9 @@ class Context:
         recs = np.ascontiguousarray(records, dtype=np.uint16)
         if len(recs) != len(keys):
             raise ValueError("import_table: %d keys, %d records" % (len(keys), len(recs)))
-        w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(root, self.words))
         n = ctypes.c_uint64()
         r = ctypes.c_uint16()
-        _lib.check(self.L.gm_import(self.h, w, keys.ctypes.data if len(keys) else None,
+        _lib.check(self.L.gm_import(self.h, self._words(root), keys.ctypes.data if len(keys) else None,
                                     recs.ctypes.data if len(recs) else None, len(keys), ctypes.byref(n),
                                     ctypes.byref(r)))
         return n.value, r.value
@@ -146,25 +146,16 @@ class Context:
     def export(self):
         """Sorted keys and records (multi-word keys: an (n, words) uint64 array)."""
         n = ctypes.c_uint64()
-        if self.words > 1:
-            _lib.check(self.L.gm_export_key(self.h, None, None, 0, ctypes.byref(n)))
-            keys = np.empty((n.value, self.words), dtype=np.uint64)
-            recs = np.empty(n.value, dtype=np.uint16)
-            _lib.check(self.L.gm_export_key(self.h, keys.ctypes.data, recs.ctypes.data, n.value, ctypes.byref(n)))
-            return keys[:n.value], recs[:n.value]
-        _lib.check(self.L.gm_export(self.h, None, None, 0, ctypes.byref(n)))
-        keys = np.empty(n.value, dtype=np.uint64)
+        _lib.check(self.L.gm_export_key(self.h, None, None, 0, ctypes.byref(n)))
+        keys = np.empty((n.value, self.words), dtype=np.uint64)
         recs = np.empty(n.value, dtype=np.uint16)
-        _lib.check(self.L.gm_export(self.h, keys.ctypes.data, recs.ctypes.data, n.value, ctypes.byref(n)))
-        return keys[:n.value], recs[:n.value]
+        _lib.check(self.L.gm_export_key(self.h, keys.ctypes.data, recs.ctypes.data, n.value, ctypes.byref(n)))
+        return self._keys(keys[:n.value]), recs[:n.value]
 
     def query(self, keys):
         keys = self.key_array(keys)
         out = np.empty(len(keys), dtype=np.uint16)
-        if self.words > 1:
-            _lib.check(self.L.gm_query_key(self.h, keys.ctypes.data, out.ctypes.data, len(keys)))
-        else:
-            _lib.check(self.L.gm_query(self.h, keys.ctypes.data, out.ctypes.data, len(keys)))
+        _lib.check(self.L.gm_query_key(self.h, keys.ctypes.data, out.ctypes.data, len(keys)))
         return out
 
     def draw_count(self):
@@ -214,26 +205,18 @@ class Context:
                                     recs.ctypes.data if cap else None, cap, ctypes.byref(n)))
         m = min(cap, n.value)
         if as_array:
-            return n.value, (keys[:m] if self.words > 1 else keys[:m, 0]), recs[:m]
-        if self.words == 1:
-            return n.value, [int(k) for k in keys[:m, 0]], recs[:m]
+            return n.value, self._keys(keys[:m]), recs[:m]
         return n.value, [_lib.words_to_int(keys[i]) for i in range(m)], recs[:m]
 
     def poke(self, key, record):
         """gm_poke (test hook): overwrite one held position's record; 0xFFFF removes it."""
-        w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
-        _lib.check(self.L.gm_poke(self.h, w, int(record)))
+        _lib.check(self.L.gm_poke(self.h, self._words(key), int(record)))
 
     def expand(self, key):
         """gm_expand_host: (primitive code, children in the plugin's gen_moves order, tier)."""
         n, p, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
         kids = (ctypes.c_uint64 * (64 * self.words))()
-        if self.words > 1:
-            w = (ctypes.c_uint64 * self.words)(*_lib.int_to_words(key, self.words))
-            _lib.check(self.L.gm_expand_host_key(self.h, w, kids, 64, ctypes.byref(n), ctypes.byref(p),
-                                                 ctypes.byref(t)))
-        else:
-            _lib.check(self.L.gm_expand_host(self.h, int(key), kids, 64, ctypes.byref(n), ctypes.byref(p),
+        _lib.check(self.L.gm_expand_host_key(self.h, self._words(key), kids, 64, ctypes.byref(n), ctypes.byref(p),
                                              ctypes.byref(t)))
         W = self.words
         return p.value, [_lib.words_to_int(kids[W * i:W * i + W]) for i in range(n.value)], t.value
@@ -275,7 +258,7 @@ class Context:
             _lib.check(rc)
             break
         t = total.value
-        return heads, (ck[:t] if self.words > 1 else ck[:t, 0]), cr[:t]
+        return heads, self._keys(ck[:t]), cr[:t]
 
     def reach(self, starts, mover=_lib.REACH_ALL, other=_lib.REACH_ALL, max_plies=0, cap=0, plies=True):
         """gm_reach: the positions reachable from `starts` (keys as query() takes them) when the
@@ -308,7 +291,7 @@ class Context:
         if not cap:
             return out.as_dict(), pcs, None, None, None
         m = min(cap, out.n)
-        return out.as_dict(), pcs, (kw[:m] if self.words > 1 else kw[:m, 0]), rr[:m], ss[:m]
+        return out.as_dict(), pcs, self._keys(kw[:m]), rr[:m], ss[:m]
 
     def stats(self):
         s = _lib.Stats()

@@ -240,6 +240,34 @@ def test_othello_8x8_key_words_round_trip():
     ctx.close()
 
 
+def test_one_word_calls_refuse_a_wide_context_without_a_device():
+    """The refusals of the one-word calls on a multi-word context are the ABI functions' own
+    (GM_E_ARG, before anything asks for a device), and the *_key forms of the two host-only calls
+    answer: the initial position, and its four children."""
+    L = _lib.lib()
+    h = ctypes.c_void_p()
+    _lib.check(L.gm_open(OTH, (ctypes.c_int32 * 2)(8, 8), 2, -1, ctypes.byref(h)))
+    E_ARG = -1
+    assert L.gm_key_words(h) == 3
+    k, n, p, t = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    nn, r = ctypes.c_uint64(), ctypes.c_uint16()
+    kids1 = (ctypes.c_uint64 * 64)()
+    assert L.gm_solve(h, 0, ctypes.byref(nn), ctypes.byref(r)) == E_ARG
+    assert b"gm_solve_key" in L.gm_last_error()          # the message names the call to use instead
+    assert L.gm_pack_initial(h, ctypes.byref(k)) == E_ARG
+    assert b"gm_pack_initial_key" in L.gm_last_error()
+    assert L.gm_expand_host(h, 0, kids1, 64, ctypes.byref(n), ctypes.byref(p), ctypes.byref(t)) == E_ARG
+    assert b"gm_expand_host_key" in L.gm_last_error()
+    w = (ctypes.c_uint64 * 3)()
+    assert L.gm_pack_initial_key(h, w) == 0
+    start = _lib.words_to_int(w)
+    assert start == games.OthelloCodec(8, 8).key(load_plugin("test_games/othello_bit_new.py").initial_position())
+    kids = (ctypes.c_uint64 * (3 * 64))()
+    assert L.gm_expand_host_key(h, w, kids, 64, ctypes.byref(n), ctypes.byref(p), ctypes.byref(t)) == 0
+    assert (n.value, p.value, t.value) == (4, 4, 12)
+    L.gm_close(h)
+
+
 @pytest.mark.parametrize("rel,name", [("test_games/mttt.py", "mttt"), ("test_games/four_to_one.py", "four_to_one")])
 def test_reference_plugin_files_route_to_descriptors(rel, name):
     """The reference's own plugin files are bound by their code: plugin_fingerprints.json holds

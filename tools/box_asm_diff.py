@@ -25,7 +25,8 @@ def kernels(path):
             line = line.split(";")[0].strip()
             if not line or line.startswith(".") or line.endswith(":"):
                 continue
-            ins.append(line)
+            # a local label carries the function's number in the file, which moves with the order of emission
+            ins.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
         vg = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1))
         sc = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc)
         out[name] = (ins, vg, int(sc.group(1)) if sc else 0)
