@@ -1387,8 +1387,27 @@ __global__ __launch_bounds__(64, GM_BOX_WAVES) void box_split_flow_kernel(const 
     }
 }
 
-__global__ void box_epoch_kernel(uint32_t *epoch) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *epoch += 1u;
+// The last node of every one-GPU box solve (one workgroup, one wave): hands the host what it
+// waits for and leaves the dataflow state ready for the next solve, so nothing stands in front
+// of a solve's first launch and no copy behind its last.  res (pinned host memory, DenseBox::h_res):
+// [0] the root's code, [1], [2] the dataflow error words (flow null: tier launches only, zero).
+// Then the error words are zeroed and the epoch moves on, past 0, the value fresh flags hold.
+__global__ __launch_bounds__(64) void box_result_kernel(const uint8_t *__restrict__ root_code, uint32_t *flow,
+                                                        uint32_t *res) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t code = *root_code;
+    // (read as bx_wait reads them: the waves that time out set them with device-scope atomics)
+    const uint32_t e0 = flow ? __hip_atomic_load(&flow[8], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    const uint32_t e1 = flow ? __hip_atomic_load(&flow[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    __hip_atomic_store(&res[0], code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&res[1], e0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&res[2], e1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (flow) {
+        flow[8] = 0u;
+        flow[9] = 0u;
+        const uint32_t ep = flow[16] + 1u;
+        flow[16] = ep ? ep : 1u;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1489,17 +1508,24 @@ int box_split_flow_resident(int device) {
 // Measured: the thin tiers alone, (10, 30), gain nothing over tier launches;
 // the ramp tiers pay.  With two mirrors the gain ended at (14, 26) (from (16, 24) on the thick
 // tiers' sc1 child loads lost); with the heap-2/3 mirror in the dataflow launches a tier costs
-// them 10/16 of the groups it costs a tier launch, and (16, 24) is the fastest of the candidates.
+// them 10/16 of the groups it costs a tier launch, and every tier moved from a tier launch into
+// them still pays: of (16, 24), (17, 23), (18, 22) and (19, 21) each is faster than the one before
+// (profiles/result_node/).  (19, 21) leaves the solve's kernel time 1.664-1.682 ms, the headline's
+// roofline.frac at most 0.968: the project keeps it <= 0.97 (1.660 ms), so the range ends here.
 #ifndef GM_BOX_HYBRID_LO
-#define GM_BOX_HYBRID_LO 16
+#define GM_BOX_HYBRID_LO 19
 #endif
 #ifndef GM_BOX_HYBRID_HI
-#define GM_BOX_HYBRID_HI 24
+#define GM_BOX_HYBRID_HI 21
 #endif
 constexpr int BOX_HYBRID_OFF_HI = 40;
 
 struct DenseBox {
     uint32_t root_hi = 0;
+    // the root the per-root state is of (dense_box_solve): its tier counts and the result node's
+    // address of the root's code; two roots of one top box share everything else
+    uint64_t root = ~0ull;
+    std::vector<uint64_t> tier_counts;
     uint8_t *table = nullptr;
     bool owned = false;
     uint32_t *d_boxes = nullptr;
@@ -1524,7 +1550,10 @@ struct DenseBox {
     bool flow = false;                // one-launch (dataflow) solve (GM_OPT_BOX_FLOW)
     int flow_grid = 0;                // the dataflow launch's grid: its resident capacity
     size_t flow_dyn = 0;              // dynamic LDS of the dataflow launch (GM_BOX_FLOW_EXTRA_LDS, tests)
-    uint32_t *d_flow = nullptr;       // [0, 9) error word at [8] (hybrid: the tail's at [9]), [16] epoch, [64, 64 + 2^20) box flags
+    // [8] error word (hybrid: the head's, the tail's at [9]), [16] epoch, [64, 64 + 2^20) box flags.
+    // Between two solves the error words are zero and the epoch is the next solve's: set at
+    // prepare, kept so by box_result_kernel at the end of every solve.
+    uint32_t *d_flow = nullptr;
     uint32_t *d_groups = nullptr;     // the 8 group queues (BxFlow)
     uint32_t qbase[8] = {}, qlen[8] = {};
     // hybrid schedule (GM_BOX_HYBRID): box-tiers [0, hyb_lo) in one dataflow launch over the compute
@@ -1534,8 +1563,12 @@ struct DenseBox {
     bool hyb = false;                 // some box-tier runs in a dataflow launch
     uint32_t hqbase[2][8] = {}, hqlen[2][8] = {};
     int hyb_grid[2] = {0, 0};
-    uint32_t *h_res = nullptr;        // pinned: [0] the root's code (low byte), [1], [2] the dataflow error words
+    // pinned, written by box_result_kernel through d_res (its device address; both from prepare:
+    // d_res is an argument of the captured graph): [0] the root's code, BOX_RES_PENDING until the
+    // kernel has run, [1], [2] the dataflow error words
+    uint32_t *h_res = nullptr, *d_res = nullptr;
 };
+constexpr uint32_t BOX_RES_PENDING = 0xFFFFFFFFu;   // no code: a code is a byte
 
 // GM_BOX_FLOW (development, overrides GM_OPT_BOX_FLOW): 0 tier launches, 1 dataflow, 2 dataflow
 // without its waits (wrong results: times everything else)
@@ -1698,6 +1731,8 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
         const size_t words = 64 + (1u << 20);
         GM_HIP(hipMalloc(&d->d_flow, words * 4));
         GM_HIP(hipMemset(d->d_flow, 0, words * 4));
+        const uint32_t first_epoch = 1;   // (0 is what the fresh flags hold)
+        GM_HIP(hipMemcpy(d->d_flow + 16, &first_epoch, 4, hipMemcpyHostToDevice));
         std::vector<uint32_t> qs;
         if (d->flow) {
             box_flow_queues(d->boxes, d->tier_off, 0, nt, false, d->qbase, d->qlen, qs);
@@ -1738,12 +1773,14 @@ static int box_prepare(Ctx *c, DenseBox *d, uint64_t root) {
     }
     GM_HIP(hipMalloc(&d->d_tables, sizeof(uint8_t *)));
     GM_HIP(hipMemcpy(d->d_tables, &d->table, sizeof(uint8_t *), hipMemcpyHostToDevice));
+    GM_HIP(hipHostMalloc((void **)&d->h_res, 3 * 4, hipHostMallocDefault));
+    GM_HIP(hipHostGetDevicePointer((void **)&d->d_res, d->h_res, 0));
     return GM_OK;
 }
 
 // The whole-solve dataflow launch (range < 0), or launch `range` (0 head, 1 tail) of the hybrid
-// schedule: its own queues and error word, the epoch the head's (the two launches' box sets
-// are disjoint, so one epoch serves both; the tail bumps it when there is no head).
+// schedule: its own queues and error word, one epoch per solve (the two launches' box sets
+// are disjoint, so one epoch serves both).
 static int box_launch_flow(Ctx *c, DenseBox *d, int range = -1) {
     BxFlow F;
     F.groups = d->d_groups;
@@ -1761,13 +1798,10 @@ static int box_launch_flow(Ctx *c, DenseBox *d, int range = -1) {
     const double ms = tm ? atof(tm) : 200.0;
     if (!(ms > 0.0)) { set_error("GM_BOX_FLOW_TIMEOUT_MS must be > 0 (got %s)", tm); return GM_E_ARG; }
     F.timeout = (uint64_t)(ms * 100000.0);
-    // The kernel uses no word of ctr but the error word, and the hybrid's two lie side by side:
-    // the first range launch of a solve resets both in one memset node and bumps the epoch
-    // (each extra node between two launches costs the solve 3-5 us).
-    const bool first = range < 1 || !d->hyb_grid[0];
-    if (range < 0) GM_HIP(hipMemsetAsync(F.ctr, 0, 9 * 4, c->stream));
-    else if (first) GM_HIP(hipMemsetAsync(d->d_flow + 8, 0, 2 * 4, c->stream));
-    if (first) hipLaunchKernelGGL(box_epoch_kernel, dim3(1), dim3(64), 0, c->stream, d->d_flow + 16);
+    // The kernel uses no word of ctr but the error word, and the hybrid's two lie side by side.
+    // Nothing is enqueued in front of the launch (each extra node between two launches costs the
+    // solve 3-5 us): the error words are zero and the epoch is this solve's already, left so by
+    // box_prepare or by the result node of the solve before (box_launch_tiers).
     if (range < 0)
         hipLaunchKernelGGL(box_flow_kernel<false>, dim3((uint32_t)d->flow_grid), dim3(64), d->flow_dyn, c->stream,
                            d->table, d->d_boxes, (const uint32_t *)nullptr, (const uint32_t *)nullptr, F);
@@ -1778,8 +1812,20 @@ static int box_launch_flow(Ctx *c, DenseBox *d, int range = -1) {
     return GM_OK;
 }
 
+// The solve's last node (box_result_kernel): the root's code and the error words to h_res, the
+// dataflow state made ready for the next solve.
+static int box_launch_result(Ctx *c, DenseBox *d) {
+    hipLaunchKernelGGL(box_result_kernel, dim3(1), dim3(64), 0, c->stream,
+                       (const uint8_t *)d->table + box_index_of_key((uint32_t)d->root), d->d_flow, d->d_res);
+    GM_HIP(hipGetLastError());
+    return GM_OK;
+}
+
 static int box_launch_tiers(Ctx *c, DenseBox *d) {
-    if (d->flow) return box_launch_flow(c, d);
+    if (d->flow) {
+        GM_TRY(box_launch_flow(c, d));
+        return box_launch_result(c, d);
+    }
     // hybrid schedule: the head's tiers, then tier launches, then the tail's, all on the one stream
     const size_t nt = d->tier_off.size() - 1;
     const size_t h0 = d->hyb ? std::min<size_t>((size_t)d->hyb_lo, nt) : 0;
@@ -1808,8 +1854,7 @@ static int box_launch_tiers(Ctx *c, DenseBox *d) {
                            (uint8_t *)nullptr, cnb);
     }
     if (d->hyb_grid[1]) GM_TRY(box_launch_flow(c, d, 1));
-    GM_HIP(hipGetLastError());
-    return GM_OK;
+    return box_launch_result(c, d);
 }
 
 // (the hybrid schedule counts as its box-tiers: gm_stats_t.kernel_launches is the tier count)
@@ -1849,11 +1894,18 @@ static int dense_box_solve(Ctx *c, const void *root_key) {
             return rc;
         }
     }
+    if (d->root != root) {   // once per root, not per solve (the captured graph holds the root's address)
+        d->root = root;
+        box_tier_counts(root, d->tier_counts);
+        if (d->graph) { (void)hipGraphExecDestroy(d->graph); d->graph = nullptr; }
+    }
     const double t0 = now_ms();
     if (c->timing && !d->ev[0]) {
         GM_HIP(hipEventCreate(&d->ev[0]));
         GM_HIP(hipEventCreate(&d->ev[1]));
     }
+    d->h_res[0] = BOX_RES_PENDING;
+    d->h_res[1] = d->h_res[2] = 0;
     if (c->use_graph) {
         if (!d->graph || d->graph_stream != c->stream) {
             if (d->graph) { (void)hipGraphExecDestroy(d->graph); d->graph = nullptr; }
@@ -1861,7 +1913,7 @@ static int dense_box_solve(Ctx *c, const void *root_key) {
             GM_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
             const int rc = box_launch_tiers(c, d);
             const hipError_t e = hipStreamEndCapture(c->stream, &g);
-            if (rc != GM_OK) return rc;
+            if (rc != GM_OK) return rc;   // (captured, not run: the dataflow state is untouched)
             if (e != hipSuccess) { set_error("graph capture failed: %s", hipGetErrorString(e)); return GM_E_HIP; }
             GM_HIP(hipGraphInstantiate(&d->graph, g, nullptr, nullptr, 0));
             GM_HIP(hipGraphDestroy(g));
@@ -1872,7 +1924,9 @@ static int dense_box_solve(Ctx *c, const void *root_key) {
         if (c->timing) GM_HIP(hipEventRecord(d->ev[1], c->stream));
     } else {
         if (c->timing) GM_HIP(hipEventRecord(d->ev[0], c->stream));
-        GM_TRY(box_launch_tiers(c, d));
+        // (launches that stop half-way leave flags of this epoch and no result node to move it
+        // on: the next solve must not find them, so the context is not kept)
+        if (const int rc = box_launch_tiers(c, d)) { dense_box_free(c); return rc; }
         if (c->timing) GM_HIP(hipEventRecord(d->ev[1], c->stream));
     }
 #if GM_BOX_FLOW_TRACE
@@ -1901,13 +1955,16 @@ static int dense_box_solve(Ctx *c, const void *root_key) {
                 h[7] / (double)(h[6] ? h[6] : 1) / 100.0, h[5] / (double)(h[7] ? h[7] : 1) / 10.0);
     }
 #endif
-    // the root's code and the dataflow error word in one pinned buffer: one wait per solve
-    if (!d->h_res) GM_HIP(hipHostMalloc((void **)&d->h_res, 12, hipHostMallocDefault));
-    d->h_res[0] = d->h_res[1] = d->h_res[2] = 0;
-    GM_HIP(hipMemcpyAsync(d->h_res, d->table + box_index_of_key((uint32_t)root), 1, hipMemcpyDeviceToHost, c->stream));
-    if (d->flow || d->hyb) GM_HIP(hipMemcpyAsync(d->h_res + 1, d->d_flow + 8, 8, hipMemcpyDeviceToHost, c->stream));
+    // the root's code and the dataflow error words are in the pinned buffer when the solve's last
+    // node (box_result_kernel) has run: one wait per solve, no copy
     GM_HIP(hipStreamSynchronize(c->stream));
-    const uint8_t rs = (uint8_t)(d->h_res[0] & 0xFFu);
+    const uint32_t res0 = __atomic_load_n(&d->h_res[0], __ATOMIC_ACQUIRE);
+    if (res0 == BOX_RES_PENDING) {
+        set_error("box solve: the result node did not deliver the root's code");
+        dense_box_free(c);   // (nor moved the epoch on: the next solve prepares afresh)
+        return GM_E_HIP;
+    }
+    const uint8_t rs = (uint8_t)(res0 & 0xFFu);
     if ((d->flow || d->hyb) && (d->h_res[1] | d->h_res[2])) {
         // A wait timed out: solve again with the tier launches.  The context keeps tier
         // launches from then on (box_flow_failed, cleared by gm_set_option GM_OPT_BOX_FLOW);
@@ -1926,7 +1983,7 @@ static int dense_box_solve(Ctx *c, const void *root_key) {
     uint64_t n = 1;
     for (int j = 0; j < 8; j++) n *= ((root >> (4 * j)) & 15u) + 1;
     c->n_positions = n;
-    box_tier_counts(root, c->tier_counts);
+    c->tier_counts = d->tier_counts;   // (another engine may have solved on this context in between)
     c->stats.n_positions = n;
     c->stats.n_primitive = 1;
     c->stats.n_tiers = (int)d->tier_off.size() - 1;
