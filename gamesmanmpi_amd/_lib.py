@@ -11,7 +11,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # GM_LIB_PATH: development aid to load an experimental build of the same library
 LIB_PATH = os.environ.get("GM_LIB_PATH") or os.path.join(PKG, "libgmsolve.so")
 
-GAME_FOUR_TO_ONE, GAME_TTT, GAME_TOOT, GAME_OTHELLO, GAME_SUBTRACT, GAME_GRAPH = 1, 2, 3, 4, 5, 6
+GAME_FOUR_TO_ONE, GAME_TTT, GAME_TOOT, GAME_OTHELLO, GAME_SUBTRACT, GAME_GRAPH, GAME_CONNECT = 1, 2, 3, 4, 5, 6, 7
 ENGINE_AUTO, ENGINE_DENSE, ENGINE_SPARSE, ENGINE_DIST_DENSE, ENGINE_DIST_SPARSE, ENGINE_GRAPH = 0, 1, 2, 3, 4, 5
 OPT_ENGINE, OPT_SUB_LOW, OPT_GRAPH, OPT_TIMING, OPT_VIRTUAL_RANKS, OPT_SUB_THREADS = 1, 2, 3, 4, 5, 6
 OPT_SUB_INTERLEAVE = 7

@@ -271,6 +271,140 @@ GM_HD DescToot unreduced(const DescToot &d) {
     return r;
 }
 
+// ---------------------------------------------------------------- Connect (k in a row with gravity)
+// test_games/connect4.py: L columns of H rows, a disc falls to the lowest empty cell of its
+// column, `K` in a row (horizontal, vertical, either diagonal) of the player who just moved is
+// a LOSS for the player to move, a full board without one a TIE.  The first player moves when
+// the disc count is even.
+// Key = one field of H + 1 bits per column, column x at bits [x (H+1), (x+1) (H+1)): a column
+// of h discs holds 2^h + s, s = bit y set iff the disc in row y (0 = bottom) is the first
+// player's -- the stones below a single cap bit; the empty board is one set bit per column.
+// A move in column x adds cap_x (second player) or 2 cap_x (first player).  L (H+1) <= 63:
+// no key reaches EMPTY_KEY, and the radix sort's end bit stays below 64 (sparse.hip).
+// Bit H of a column is never a stone, so a shift by 1, H+1, H or H+2 cannot carry a run of
+// stones from one column's top into the next one's bottom: the line tests need no start masks.
+struct DescConnect {
+    static constexpr int MAX_SKIP = 1;
+    static constexpr int MAXC = 16;
+    int L, H, K, H1, bits;
+    uint32_t stride[4];       // vertical, horizontal, the two diagonals (63 where none fits: L = 1)
+    uint64_t bottom;          // bit 0 of every column
+    uint64_t top;             // bit H of every column (a full column's cap)
+    uint64_t smear[6];        // a shift down by 1, 2, 4, 8, 16, 32 kept inside its column
+    // left-right mirror symmetry (set per solve, gm_api.hip: only when the root is its own
+    // mirror image): the rules are mirror-invariant -- the mirror keeps rows and columns and
+    // swaps the two diagonals -- so a position and its mirror image share value and
+    // remoteness, and with sym set visit() returns min(child, mirror(child)).
+    uint32_t sym = 0;
+
+    static bool make(int L_, int H_, int K_, DescConnect *d) {
+        if (L_ < 1 || L_ > 16 || H_ < 1 || H_ > 62 || K_ < 2 || K_ > 8 || L_ * (H_ + 1) > 63) return false;
+        d->L = L_; d->H = H_; d->K = K_; d->H1 = H_ + 1; d->bits = L_ * (H_ + 1);
+        const int st[4] = {1, H_ + 1, H_, H_ + 2};
+        for (int i = 0; i < 4; i++) d->stride[i] = (uint32_t)(st[i] < 63 ? st[i] : 63);
+        d->bottom = d->top = 0;
+        for (int x = 0; x < L_; x++) {
+            d->bottom |= 1ull << (x * d->H1);
+            d->top |= 1ull << (x * d->H1 + H_);
+        }
+        for (int j = 0; j < 6; j++) {
+            const int s = 1 << j;
+            uint64_t m = 0;   // the bits a shift down by s lands on from its own column: rows 0 .. H - s
+            for (int x = 0; x < L_; x++)
+                for (int y = 0; y + s <= H_; y++) m |= 1ull << (x * d->H1 + y);
+            d->smear[j] = m;
+        }
+        return true;
+    }
+    // every column's cap and the cells below it
+    GM_HD uint64_t filled(uint64_t k) const {
+        uint64_t m = k;
+        m |= (m >> 1) & smear[0];
+        m |= (m >> 2) & smear[1];
+        m |= (m >> 4) & smear[2];
+        if (H > 7) {   // columns of more than 8 bits (a board of at most 7 columns)
+            m |= (m >> 8) & smear[3];
+            m |= (m >> 16) & smear[4];
+            m |= (m >> 32) & smear[5];
+        }
+        return m;
+    }
+    GM_HD uint64_t occupied(uint64_t k) const { return (filled(k) >> 1) & smear[0]; }
+    // K stones of b in a row along any of the four directions
+    GM_HD bool line(uint64_t b) const {
+        uint64_t any = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint64_t r = b;
+            for (int j = 1; j < K; j++) r &= r >> stride[i];
+            any |= r;
+        }
+        return any != 0;
+    }
+    GM_HD int primitive(uint64_t k) const {
+        const uint64_t occ = occupied(k);
+        const int discs = popc64(occ);
+        // the stones of the player who is not to move: the first player's when the count is odd
+        const uint64_t last = (discs & 1) ? (k & occ) : (occ & ~k);
+        if (line(last)) return LOSS;
+        return discs == L * H ? TIE : UNDECIDED;
+    }
+    GM_HD uint64_t mirror(uint64_t k) const {
+        const uint64_t col = (1ull << H1) - 1ull;
+        for (int x = 0; 2 * x < L - 1; x++) {
+            const int lo = x * H1, d = (L - 1 - 2 * x) * H1;
+            const uint64_t t = ((k >> d) ^ k) & (col << lo);
+            k ^= t | (t << d);
+        }
+        return k;
+    }
+    GM_HD uint64_t canon(uint64_t k) const {
+        if (!sym) return k;
+        const uint64_t m = mirror(k);
+        return m < k ? m : k;
+    }
+    template <class F>
+    GM_HD void orbit(uint64_t k, F &&f) const {
+        f(k);
+        if (sym) {
+            const uint64_t m = mirror(k);
+            if (m != k) f(m);
+        }
+    }
+    template <class F>
+    GM_HD void visit(uint64_t k, F &&f) const {
+        const uint64_t fl = filled(k), occ = (fl >> 1) & smear[0];
+        const int first = !(popc64(occ) & 1);          // the first player moves on an even count
+        for (uint64_t m = (fl ^ occ) & ~top; m; m &= m - 1) {   // the caps of the open columns, ascending
+            const uint64_t cap = m & (~m + 1);
+            if (!f(canon(k + (cap << first)))) return;
+        }
+    }
+    GM_HD int children(uint64_t k, uint64_t *out) const { return collect(*this, k, out); }
+    // classify's edge counts without making the children: one per open column, one disc deeper
+    static constexpr bool STEP_COUNT = true;
+    GM_HD int count_children(uint64_t k, int *dt) const {
+        const uint64_t fl = filled(k);
+        *dt = 1;
+        return popc64((fl ^ ((fl >> 1) & smear[0])) & ~top);
+    }
+    GM_HD int64_t tier(uint64_t k) const { return popc64(occupied(k)); }
+    GM_HD bool valid(uint64_t k) const {
+        if (k >> bits) return false;
+        const uint64_t fl = filled(k);
+        if ((fl & bottom) != bottom) return false;      // an empty column field
+        const uint64_t occ = (fl >> 1) & smear[0];
+        const int discs = popc64(occ);
+        return popc64(k & occ) == (discs + 1) / 2;
+    }
+};
+
+GM_HD DescConnect unreduced(const DescConnect &d) {
+    DescConnect r = d;
+    r.sym = 0;
+    return r;
+}
+
 
 // ---------------------------------------------------------------- Othello
 // reference test_games/othello_bit_new.py (square boards).  Key = all 2A+16

@@ -443,12 +443,13 @@ static int parse_root(const Ctx *c, const uint64_t *words, const char *call, Roo
     return GM_OK;
 }
 // ... and made the context's after it, with the symmetry reduction of a solve from it (games.hpp):
-// Toot-and-Otto's mirror when the root is its own mirror image, Othello's board symmetries that
+// Toot-and-Otto's and Connect's mirror when the root is its own mirror image, Othello's board symmetries that
 // fix the root (DescOthello::sym)
 static void set_root(Ctx *c, const Root &r) {
     c->root = r.one;
     if (c->wide) memcpy(&c->root_wide, r.wide.p, sizeof c->root_wide);
     if (c->game == GM_GAME_TOOT) c->toot.sym = (c->symmetry && c->toot.mirror(c->root) == c->root) ? 1u : 0u;
+    if (c->game == GM_GAME_CONNECT) c->con.sym = (c->symmetry && c->con.mirror(c->root) == c->root) ? 1u : 0u;
     if (c->game == GM_GAME_OTHELLO && !c->wide) c->oth.sym = c->symmetry ? c->oth.stabilizer(c->root) : 0u;
 }
 
@@ -555,6 +556,10 @@ int gm_open(int game, const int32_t *params, int nparams, int device, gm_ctx **o
     case GM_GAME_SUBTRACT:
         c->sub.heaps = nparams > 0 ? params[0] : 8;
         ok = c->sub.heaps >= 1 && c->sub.heaps <= 8;
+        break;
+    case GM_GAME_CONNECT:
+        ok = DescConnect::make(nparams > 0 ? params[0] : 5, nparams > 1 ? params[1] : 4, nparams > 2 ? params[2] : 4,
+                               &c->con);
         break;
     default:
         ok = false;
@@ -707,6 +712,7 @@ int gm_pack_initial(gm_ctx *h, uint64_t *key) {
         return GM_OK;
     }
     case GM_GAME_SUBTRACT: *key = (1ull << (4 * c->sub.heaps)) - 1; return GM_OK;
+    case GM_GAME_CONNECT: *key = c->con.bottom; return GM_OK;   // every column's cap at row 0
     }
     return GM_E_GAME;
 }
@@ -720,7 +726,7 @@ int gm_expand_host(gm_ctx *h, uint64_t key, uint64_t *children, int cap, int *n,
     int64_t t = 0;
     if (!key_valid(c, key)) { set_error("key is not a valid position"); return GM_E_KEY; }
     GM_TRY(with_desc(c, [&](const auto &reduced) {
-        const auto d = unreduced(reduced);   // the plugin's own moves: no symmetry reduction (Toot, Othello)
+        const auto d = unreduced(reduced);   // the plugin's own moves: no symmetry reduction (Toot, Connect, Othello)
         p = d.primitive(key);
         t = d.tier(key);
         if (p == UNDECIDED) k = d.children(key, kids);

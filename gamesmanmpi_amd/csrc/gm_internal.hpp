@@ -76,6 +76,7 @@ struct Ctx {
     DescF2O f2o;
     DescTTT ttt;
     DescToot toot;
+    DescConnect con;
     DescOthello oth;
     DescSub sub;
     DescOthello8 oth8;       // GM_GAME_OTHELLO at 8x8: 128-bit keys (wide)
@@ -297,7 +298,7 @@ inline int query_keys(Ctx *c, const uint64_t *keys, uint16_t *recs, uint64_t n, 
     return GM_OK;
 }
 
-// call f with the context's game descriptor: the five games with 64-bit keys
+// call f with the context's game descriptor: the six games with 64-bit keys
 template <class C, class F>
 inline int with_desc(C *c, F &&f) {
     switch (c->game) {
@@ -306,6 +307,7 @@ inline int with_desc(C *c, F &&f) {
     case GM_GAME_TOOT: return f(c->toot);
     case GM_GAME_OTHELLO: return f(c->oth);
     case GM_GAME_SUBTRACT: return f(c->sub);
+    case GM_GAME_CONNECT: return f(c->con);
     }
     set_error("unknown game");
     return GM_E_GAME;

@@ -405,6 +405,7 @@ static int key_bits(const Ctx *c) {
     case GM_GAME_OTHELLO: return 2 * c->oth.A + 16;
     case GM_GAME_TTT: return 15;
     case GM_GAME_SUBTRACT: return 4 * c->sub.heaps;
+    case GM_GAME_CONNECT: return c->con.bits;
     }
     return 64;
 }
@@ -496,6 +497,7 @@ static bool replay_enabled() {
 static void plan_key_of(const Ctx *c, uint64_t root, int64_t (&key)[7]) {
     const int64_t k[7] = {c->game, c->params[0], c->params[1], c->params[2], c->params[3], (int64_t)root,
                           c->game == GM_GAME_TOOT ? (int64_t)c->toot.sym
+                          : c->game == GM_GAME_CONNECT ? (int64_t)c->con.sym
                           : c->game == GM_GAME_OTHELLO ? (int64_t)c->oth.sym : 0};
     std::copy(k, k + 7, key);
 }

@@ -955,6 +955,7 @@ inline int tiers_moves(Ctx *c, const D &d, const std::vector<TierGroup<key_t<D>>
 template <class D>
 inline bool tables_reduced(const D &) { return false; }
 inline bool tables_reduced(const DescToot &d) { return d.sym != 0; }
+inline bool tables_reduced(const DescConnect &d) { return d.sym != 0; }
 inline bool tables_reduced(const DescOthello &d) { return d.sym != 0; }
 
 // gm_reach over tier tables: group g holds the keys of owner rank g (one group: the one-GPU engine)

@@ -13,7 +13,7 @@ one that differs only in deep or rare positions.  Certainty comes from one of:
   everything they reach -- module functions they call (transitively), closures
   (the ``src.utils`` encode/decode decorators), default arguments, and the values of
   the module globals they read (``BLANK``, ``MAX_TAKE``, ...).  Board dimensions
-  and heap counts (``length``, ``height``, ``area``, ``HEAPS``) are left out: they
+  and heap counts (``length``, ``height``, ``area``, ``HEAPS``, ``connect``) are left out: they
   are the descriptor's parameters, read from the module by the codec;
 * or an exhaustive cross-check of every reachable position (games.identify).
 
@@ -38,7 +38,7 @@ import types
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 STORE = os.path.join(HERE, "plugin_fingerprints.json")
-PARAM_NAMES = frozenset({"length", "height", "area", "HEAPS"})
+PARAM_NAMES = frozenset({"length", "height", "area", "HEAPS", "connect"})
 RULES = ("gen_moves", "do_move", "primitive")
 _SIMPLE = (int, float, complex, str, bytes, bool, type(None))
 
@@ -181,6 +181,7 @@ SOURCES = [
     ("test_games/toot_and_otto_bitstring.py", "toot_and_otto"),
     ("test_games/othello_bit_new.py", "othello"),
     ("test_games/subtraction.py", "subtraction"),
+    ("test_games/connect4.py", "connect4"),
 ]
 REFERENCE = "/root/reference"
 

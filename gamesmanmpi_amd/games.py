@@ -171,9 +171,43 @@ class SubtractCodec(Codec):
         return int(key)
 
 
+class ConnectCodec(Codec):
+    """Int positions of test_games/connect4.py: the position is the descriptor's key (one field
+    of height + 1 bits per column, the first player's stones below a cap bit)."""
+    game_id = _lib.GAME_CONNECT
+    name = "connect4"
+
+    def __init__(self, length, height, connect):
+        self.L, self.H, self.K = int(length), int(height), int(connect)
+        if not (1 <= self.L <= 16 and self.H >= 1 and 2 <= self.K <= 8 and self.L * (self.H + 1) <= 63):
+            raise ValueError("board does not fit a 63-bit key")
+        self.params = (self.L, self.H, self.K)
+        self.nbits = self.L * (self.H + 1)
+
+    def key(self, pos):
+        if isinstance(pos, (bool, str, np.ndarray)) or not isinstance(pos, (int, np.integer)):
+            raise ValueError("not a connect position")
+        k = int(pos)
+        if k < 0 or k >> self.nbits:
+            raise ValueError("out of range")
+        col = (1 << (self.H + 1)) - 1
+        if any(not (k >> (x * (self.H + 1))) & col for x in range(self.L)):
+            raise ValueError("a column without its cap bit")
+        return k
+
+    def pos(self, key):
+        return int(key)
+
+
 def _candidates(module):
     dims = (getattr(module, "length", None), getattr(module, "height", None))
     out = []
+    # first: FourToOneCodec and SubtractCodec take any int as well
+    if dims[0] is not None and dims[1] is not None and hasattr(module, "connect"):
+        try:
+            out.append(ConnectCodec(dims[0], dims[1], module.connect))
+        except (ValueError, TypeError):
+            pass
     if hasattr(module, "HEAPS"):
         out.append(SubtractCodec(module.HEAPS))
     out += [TTTStringCodec(), TTTNumpyCodec(), FourToOneCodec()]

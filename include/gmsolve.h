@@ -42,6 +42,10 @@ extern "C" {
  *                                              or {8, 8} with 3-word keys (gm_key_words)
  *   GM_GAME_SUBTRACT     {heaps}               (the build's synthetic game, 1..8 heaps of 4 bits)
  *   GM_GAME_GRAPH        none                  (any plugin: an explicit graph from gm_solve_graph)
+ *   GM_GAME_CONNECT      {length, height, connect}  (test_games/connect4.py: `connect` in a row with gravity;
+ *                                              defaults 5, 4, 4), 1 <= L <= 16, H >= 1, 2 <= K <= 8,
+ *                                              L*(H+1) <= 63; key = one (H+1)-bit field per column, the
+ *                                              first player's stones below a cap bit
  */
 enum {
     GM_GAME_FOUR_TO_ONE = 1,
@@ -49,7 +53,8 @@ enum {
     GM_GAME_TOOT = 3,
     GM_GAME_OTHELLO = 4,
     GM_GAME_SUBTRACT = 5,
-    GM_GAME_GRAPH = 6
+    GM_GAME_GRAPH = 6,
+    GM_GAME_CONNECT = 7
 };
 
 enum {
@@ -118,7 +123,8 @@ enum {
     GM_OPT_SYMMETRY = 14,   /* sparse engines, symmetry reduction (the reference's unused
                                hook othello_bit_new.py:224-235): 1 (default) = TOOT stores one position
                                per left-right mirror pair when the root is its own mirror image; every
-                               count, export, query and digest still covers both positions.  0 = off.
+                               count, export, query and digest still covers both positions.  CONNECT does
+                               the same with the reversal of its column fields.  0 = off.
                                Box engine (SUBTRACT, 8 heaps, one GPU, tier launches): 1 (default) = of
                                two boxes that differ by the exchange of heaps 6 and 7, and of two that
                                differ by the exchange of heaps 4 and 5, one is computed and both are

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's ``solve_local.py``: one process, one line of output.
 
-    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--remoteness] [--analysis] [--verify]
+    python solve_local.py GAME_FILE [--custom FILE --init_pos NAME] [--dims LxH] [--connect K] [--remoteness] [--analysis] [--verify]
                           [--loopy] [--load DIR] [--find SPEC ...] [--find-cap N] [--line] [--moves]
                           [--strategy [best|first]]
 
@@ -52,6 +52,7 @@ def build_parser():
     p.add_argument("--custom")
     p.add_argument("--init_pos")
     p.add_argument("--dims")
+    p.add_argument("--connect", type=int, metavar="K")
     p.add_argument("--heaps", type=int)
     p.add_argument("--remoteness", action="store_true")
     p.add_argument("--analysis", action="store_true")

@@ -27,8 +27,8 @@ Differences, on purpose:
   gamesmanmpi_amd/persist.py) -- and as ``DIR/stats/<rank>/table.npz`` (sorted
   u64 keys + u16 records); ``--sd-format`` picks one (shelves are written for
   tables of up to 2 million positions unless asked for explicitly);
-* extras: ``--dims LxH`` patches board plugins' ``length``/``height``, ``--heaps``
-  patches the subtraction plugin, ``--engine``, ``--device``, ``--stats``;
+* extras: ``--dims LxH`` patches board plugins' ``length``/``height``, ``--connect K``
+  the connect4 plugin's ``connect``, ``--heaps`` patches the subtraction plugin, ``--engine``, ``--device``, ``--stats``;
 * ``--analysis`` prints, after the root line, the whole solve's positions by value and
   remoteness (gm_histogram, gamesmanmpi_amd/analysis.py); with ``-sd DIR`` rank 0 also
   writes them to ``DIR/stats/analysis.json``;
@@ -105,6 +105,7 @@ def build_parser():
                    "If none is specified, the default is used.")
     p.add_argument("--cp", action="store_true")
     p.add_argument("--dims", help="board plugins: LxH (sets the module's length/height)")
+    p.add_argument("--connect", type=int, metavar="K", help="connect4 plugin: stones in a row that win (sets the module's connect)")
     p.add_argument("--heaps", type=int, help="subtraction plugin: number of heaps")
     p.add_argument("--engine", choices=("auto", "dense", "sparse"), default="auto")
     p.add_argument("--device", type=int, default=None)
@@ -177,6 +178,8 @@ def prepare_game(args):
         game.length, game.height = L, H
         if hasattr(game, "area"):
             game.area = L * H
+    if getattr(args, "connect", None) is not None:
+        game.connect = args.connect
     if args.heaps is not None:
         game.HEAPS = args.heaps
     validate(game)
