@@ -23,6 +23,8 @@
 // SURVEY §0.2); here each distinct position is expanded once.
 #include "sparse_tables.hpp"
 
+#include <climits>
+
 #include <hipcub/hipcub.hpp>
 
 namespace gm {
@@ -149,6 +151,14 @@ static uint64_t split_max() {
     return v;
 }
 constexpr int SPLIT_G = 16;
+// The batch sort's count is an int (hipcub::DeviceRadixSort): a tier with more interior positions
+// than that is not sorted -- its skeys stay null, so the plain and CSR kernels walk ikeys / islot
+// and the replay has nothing to sort there.  GM_SPARSE_SORT_MAX (test aid) lowers the threshold.
+static uint64_t sort_max() {
+    static const uint64_t v = getenv("GM_SPARSE_SORT_MAX") ? strtoull(getenv("GM_SPARSE_SORT_MAX"), nullptr, 10)
+                                                            : (uint64_t)INT_MAX;
+    return v < (uint64_t)INT_MAX ? v : (uint64_t)INT_MAX;
+}
 
 template <class D>
 __global__ __launch_bounds__(256) void expand_split_kernel(D d, const uint64_t *__restrict__ ikeys, uint64_t n,
@@ -422,6 +432,8 @@ static uint32_t home_loc(const Ctx *c) {
 
 // Sort a large tier's interior list by the key's top BATCH_SORT_BITS bits into
 // (skeys, sslot) for the batch kernels; the scratch is kept for the replay's sorts.
+// Called for tiers of at most sort_max() interior positions only (the solve decides; the replay
+// sorts the tiers that have skeys): the count below is an int.
 static int batch_sort(Ctx *c, Sparse *sp, SpTier &T, bool alloc) {
     // end bit at most 63: ROCm 7's radix sort with end_bit 64 on u64 keys broke the
     // (key, value) pairing of about half the pairs (Toot 6x4, whose keys use bit 63:
@@ -700,7 +712,8 @@ static int solve_with(Ctx *c, const D &d, uint64_t root) {
         sp->tiers[t].ni = sc[9];
         sp->tiers[t].tier = sp->t_root + (int64_t)t;
         if (!sp->tiers[t].ni) continue;
-        if (sp->tiers[t].ni >= split_max() && batch_enabled()) GM_TRY(batch_sort(c, sp, sp->tiers[t], true));
+        if (sp->tiers[t].ni >= split_max() && sp->tiers[t].ni <= sort_max() && batch_enabled())
+            GM_TRY(batch_sort(c, sp, sp->tiers[t], true));
         // 2. size the tables of the tiers the children land in: load <= 0.7 for the
         //    predicted distinct children; a misprediction costs one re-run
         if (sp->tiers.size() < t + S + 1) {

@@ -22,7 +22,9 @@
  * independent.  Keys follow SURVEY Appendix B.
  *
  * Pinned by: the tests/golden npz tables (canonical tables over the reference's own
- * plugin modules) and roots.json (the reference's game_tests expectations).
+ * plugin modules) and roots.json (the reference's game_tests expectations); Connect, which the
+ * reference does not have, by the connect_*.npz tables and connect.json (this repo's plugin
+ * test_games/connect4.py solved by oracle/canonical.py).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -43,12 +45,14 @@
 #define G_TOOT 3
 #define G_OTHELLO 4
 #define G_SUBTRACT 5
+#define G_CONNECT 7
 
 #define MAXKIDS 64
 
 typedef struct {
     int game;
-    int L, H;     /* board dims (toot / othello); heaps (subtract) in L */
+    int L, H;     /* board dims (toot / othello / connect); heaps (subtract) in L */
+    int K;        /* connect: stones in a row that end the game */
 } game_t;
 
 static char g_err[256];
@@ -313,6 +317,85 @@ static int sub_kids(const game_t *g, uint64_t key, uint64_t *out) {
     return n;
 }
 
+/* ------------------------------------------------------------------ Connect */
+/* This repo's test_games/connect4.py (its docstring is the rule text): L columns of H rows, a
+ * disc falls to the lowest empty cell of its column, K in a row (along a column, a row or either
+ * diagonal) of the player who just moved is a LOSS for the player to move, a full board
+ * without one a TIE; the first player moves on an even disc count.  Key (the DescConnect
+ * comment, csrc/games.hpp): column x owns the H + 1 bits from bit x (H + 1) up; of a column of
+ * h discs bit h is set (the cap), nothing above it, and bit y < h is set iff the disc in row y
+ * (0 = bottom) is the first player's.  Decoded into an array of cells and walked cell by cell
+ * with bounds checks; a field without a cap reads as an empty column (no position: the
+ * callers pass none). */
+#define CON_FIRST 1
+#define CON_SECOND 2
+typedef struct { int cell[16][62]; int h[16]; int discs; } con_t;   /* cell[x][y] */
+static int con_bit(uint64_t key, int at) { return (int)((key >> at) & 1u); }
+static void con_decode(const game_t *g, uint64_t key, con_t *s) {
+    s->discs = 0;
+    for (int x = 0; x < g->L; x++) {
+        int base = x * (g->H + 1), h = g->H;
+        while (h > 0 && !con_bit(key, base + h)) h--;
+        s->h[x] = h;
+        s->discs += h;
+        for (int y = 0; y < g->H; y++)
+            s->cell[x][y] = y >= h ? 0 : (con_bit(key, base + y) ? CON_FIRST : CON_SECOND);
+    }
+}
+static uint64_t con_encode(const game_t *g, const con_t *s) {
+    uint64_t key = 0;
+    for (int x = 0; x < g->L; x++) {
+        uint64_t bit = 1ull << (x * (g->H + 1));   /* the column's row 0 */
+        for (int y = 0; y < s->h[x]; y++, bit *= 2)
+            if (s->cell[x][y] == CON_FIRST) key += bit;
+        key += bit;   /* the cap */
+    }
+    return key;
+}
+static int con_get(const game_t *g, const con_t *s, int x, int y) {
+    if (x < 0 || y < 0 || x >= g->L || y >= g->H) return -1;
+    return s->cell[x][y];
+}
+static int con_prim_of(const game_t *g, const con_t *s) {
+    static const int dir[4][2] = {{0, 1}, {1, 0}, {1, 1}, {1, -1}};
+    const int last = (s->discs & 1) ? CON_FIRST : CON_SECOND;   /* who just moved */
+    for (int x = 0; x < g->L; x++)
+        for (int y = 0; y < s->h[x]; y++) {
+            if (s->cell[x][y] != last) continue;
+            for (int d = 0; d < 4; d++) {
+                int n = 1;
+                while (n < g->K && con_get(g, s, x + n * dir[d][0], y + n * dir[d][1]) == last) n++;
+                if (n == g->K) return LOSS;
+            }
+        }
+    return s->discs == g->L * g->H ? TIE : UNDECIDED;
+}
+static int con_prim(const game_t *g, uint64_t key) {
+    con_t s;
+    con_decode(g, key, &s);
+    return con_prim_of(g, &s);
+}
+static int con_kids(const game_t *g, uint64_t key, uint64_t *out) {
+    con_t s;
+    con_decode(g, key, &s);
+    const int mover = (s.discs & 1) ? CON_SECOND : CON_FIRST;
+    int n = 0;
+    for (int x = 0; x < g->L; x++) {   /* ascending columns: gen_moves order */
+        if (s.h[x] >= g->H) continue;
+        s.cell[x][s.h[x]] = mover;
+        s.h[x]++;
+        out[n++] = con_encode(g, &s);
+        s.h[x]--;
+        s.cell[x][s.h[x]] = 0;
+    }
+    return n;
+}
+static int64_t con_tier(const game_t *g, uint64_t key) {
+    con_t s;
+    con_decode(g, key, &s);
+    return s.discs;
+}
+
 /* ------------------------------------------------------------------ dispatch */
 static int g_prim(const game_t *g, uint64_t k) {
     switch (g->game) {
@@ -321,6 +404,7 @@ static int g_prim(const game_t *g, uint64_t k) {
     case G_TOOT: return toot_prim(g, k);
     case G_OTHELLO: return oth_prim(g, k);
     case G_SUBTRACT: return sub_prim(k);
+    case G_CONNECT: return con_prim(g, k);
     }
     return -1;
 }
@@ -331,6 +415,7 @@ static int g_kids(const game_t *g, uint64_t k, uint64_t *out) {
     case G_TOOT: return toot_kids(g, k, out);
     case G_OTHELLO: return oth_kids(g, k, out);
     case G_SUBTRACT: return sub_kids(g, k, out);
+    case G_CONNECT: return con_kids(g, k, out);
     }
     return -1;
 }
@@ -346,6 +431,7 @@ static int64_t g_tier(const game_t *g, uint64_t k) {
         return 3 * n + s.pass;
     }
     case G_SUBTRACT: { int64_t t = 0; for (int i = 0; i < g->L; i++) t += (k >> (4 * i)) & 15; return -t; }
+    case G_CONNECT: return con_tier(g, k);
     }
     return 0;
 }
@@ -366,6 +452,15 @@ static int g_make(game_t *g, int game, const int32_t *params, int nparams) {
     case G_SUBTRACT:
         g->L = nparams > 0 ? params[0] : 8;
         if (g->L < 1 || g->L > 8) { snprintf(g_err, sizeof g_err, "heaps must be 1..8"); return -1; }
+        return 0;
+    case G_CONNECT:   /* the defaults and the range of DescConnect::make */
+        g->L = nparams > 0 ? params[0] : 5;
+        g->H = nparams > 1 ? params[1] : 4;
+        g->K = nparams > 2 ? params[2] : 4;
+        if (g->L < 1 || g->L > 16 || g->H < 1 || g->H > 62 || g->K < 2 || g->K > 8 || g->L * (g->H + 1) > 63) {
+            snprintf(g_err, sizeof g_err, "connect %dx%d, %d in a row: not a board of at most 63 key bits", g->L, g->H, g->K);
+            return -1;
+        }
         return 0;
     }
     snprintf(g_err, sizeof g_err, "unknown game %d", game);
@@ -397,6 +492,11 @@ int oracle_initial(int game, const int32_t *params, int nparams, uint64_t *root)
         return 0;
     }
     case G_SUBTRACT: *root = (1ull << (4 * g.L)) - 1; return 0;
+    case G_CONNECT: {
+        con_t s; memset(&s, 0, sizeof s);   /* every column empty */
+        *root = con_encode(&g, &s);
+        return 0;
+    }
     }
     return -1;
 }
@@ -411,11 +511,31 @@ int oracle_expand(int game, const int32_t *params, int nparams, uint64_t key,
     return 0;
 }
 
+/* oracle_expand over an array of keys, for sweeps that compare every move of a whole table:
+ * prims[i] the primitive code of keys[i], counts[i] its children (0 where it is primitive), the
+ * children appended to `children` in generation order.  Returns their total, or -1 (with more
+ * than `cap` of them as well). */
+int64_t oracle_expand_many(int game, const int32_t *params, int nparams, const uint64_t *keys, uint64_t n,
+                           uint64_t *children, uint64_t cap, int32_t *counts, int32_t *prims) {
+    game_t g;
+    if (g_make(&g, game, params, nparams)) return -1;
+    uint64_t kids[MAXKIDS], total = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        prims[i] = g_prim(&g, keys[i]);
+        const int nk = prims[i] == UNDECIDED ? g_kids(&g, keys[i], kids) : 0;
+        if (nk < 0 || total + (uint64_t)nk > cap) { snprintf(g_err, sizeof g_err, "more children than the caller's %llu", (unsigned long long)cap); return -1; }
+        counts[i] = nk;
+        memcpy(children + total, kids, (size_t)nk * sizeof(uint64_t));
+        total += (uint64_t)nk;
+    }
+    return (int64_t)total;
+}
+
 /* ---------------------------------------------- open-addressing key -> record map */
 typedef struct { uint64_t *keys; uint16_t *rec; uint64_t cap, n; } map_t;
 /* 2^63 is no valid key: F2O keys are piles >= -1, TTT < 3^9, Othello < 2^48,
- * subtract < 2^32, and a Toot key with only the first T cell set would need all
- * hands empty.  (-1 = all ones IS a F2O key, so it cannot be the sentinel.) */
+ * subtract < 2^32, Connect < 2^63, and a Toot key with only the first T cell set would need
+ * all hands empty.  (-1 = all ones IS a F2O key, so it cannot be the sentinel.) */
 #define EMPTY_KEY 0x8000000000000000ull
 static uint64_t mix(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;

@@ -89,10 +89,11 @@ def test_fixture_counts_are_the_expected_ones():
         assert sum(e["per_tier"]) == n and sum(map(sum, e["histogram"])) == n
 
 
-def test_plugin_matches_the_4x4_summary():
-    """The 4x4 table is too long to solve twice in a quick test: the walk gives the positions,
-    the primitive ones and the tiers, and the fixture's records must be the canonical fold of
-    their children's records at every position."""
+def test_plugin_matches_the_4x4_summary(oracle):
+    """The 4x4 table is too long to solve twice by the Python solver in a quick test: the walk gives
+    the positions, the primitive ones and the tiers, and the fixture's records must be the canonical
+    fold of their children's records at every position.  The C oracle does solve it again: the whole
+    table, key for key."""
     import canonical
     w = walk(4, 4, 4)
     keys, recs = mcg.load_table("connect_4x4_4")
@@ -104,6 +105,8 @@ def test_plugin_matches_the_4x4_summary():
     for p, (prim, kids) in w.items():
         want = (prim, 0) if prim != UNDECIDED else canonical.fold((rec[c] >> 14, rec[c] & 0x3FFF) for c in kids)
         assert (rec[p] >> 14, rec[p] & 0x3FFF) == want, p
+    k, r = oracle.solve(_lib.GAME_CONNECT, (4, 4, 4))
+    assert np.array_equal(k, keys) and np.array_equal(r, recs)
 
 
 @pytest.mark.parametrize("L,H,K", SMALL + [(4, 4, 4)])

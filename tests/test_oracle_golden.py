@@ -4,8 +4,10 @@ The fixtures (tests/golden/*.npz, roots.json) were generated from the REFERENCE'
 own plugin modules by tests/golden/make_golden.py; live.json records that the
 reference's live engine (src/new_process.py) agrees with them on every value.
 """
+import ctypes
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -13,7 +15,10 @@ import pytest
 import canonical
 from conftest import GOLDEN, digest, golden, load_plugin
 
-F2O, TTT, TOOT, OTH, SUB = 1, 2, 3, 4, 5
+sys.path.insert(0, GOLDEN)
+import make_connect_golden as mcg  # noqa: E402
+
+F2O, TTT, TOOT, OTH, SUB, CONNECT = 1, 2, 3, 4, 5, 7
 
 CASES = [
     ("ttt", TTT, (), None),
@@ -33,6 +38,61 @@ def test_c_oracle_matches_golden(oracle, name, game, params, root):
     k, r = oracle.solve(game, params, root)
     assert np.array_equal(k, keys)
     assert np.array_equal(r, recs)
+
+
+# Connect is this repo's own plugin (test_games/connect4.py): its fixtures are that plugin solved by
+# oracle/canonical.py (tests/golden/make_connect_golden.py), and the C oracle's cell-by-cell Connect
+# must reproduce them.
+@pytest.mark.parametrize("dims", mcg.TABLES, ids=[mcg.name_of(*d) for d in mcg.TABLES])
+def test_c_oracle_matches_connect_tables(oracle, dims):
+    keys, recs = mcg.load_table(mcg.name_of(*dims))
+    k, r = oracle.solve(CONNECT, dims)
+    assert np.array_equal(k, keys)
+    assert np.array_equal(r, recs)
+
+
+CONNECT_JSON = mcg.load_json()
+
+
+@pytest.mark.parametrize("name", sorted(CONNECT_JSON))
+def test_c_oracle_matches_connect_summaries(oracle, name):
+    """Every entry of connect.json, 4x5, 5x4 and the custom 7x6 / 9x6 roots among them, through the
+    generator's own summary(); the layered solver on the same roots."""
+    e = CONNECT_JSON[name]
+    dims, root = tuple(e["dims"]), e["root"]
+    k, r = oracle.solve(CONNECT, dims, root)
+    assert e == {**e, **mcg.summary(k, r, root, *dims)}
+    n, dg, rr, tiers = oracle.solve_layered(CONNECT, dims, root)
+    assert (n, dg, rr, tiers) == (e["positions"], e["digest"], e["root_record"], e["per_tier"])
+
+
+def test_c_oracle_connect_defaults_and_range(oracle):
+    """The defaults and the accepted range of DescConnect::make (csrc/games.hpp)."""
+    assert oracle.initial(CONNECT, ()) == oracle.initial(CONNECT, (5, 4, 4)) == sum(1 << (5 * x) for x in range(5))
+    assert oracle.initial(CONNECT, (6,)) == oracle.initial(CONNECT, (6, 4, 4))
+    root = ctypes.c_uint64()
+    for params in [(7, 6, 4), (9, 6, 4), (1, 62, 4), (16, 2, 8), (5, 4, 2), (16, 1, 2)]:
+        p, n = oracle._params(params)
+        assert oracle.L.oracle_initial(CONNECT, p, n, ctypes.byref(root)) == 0, params
+    for params in [(8, 7, 4), (17, 2, 4), (5, 4, 1), (5, 4, 9), (0, 4, 4), (5, 0, 4), (1, 63, 4)]:
+        p, n = oracle._params(params)
+        assert oracle.L.oracle_initial(CONNECT, p, n, ctypes.byref(root)) == -1, params
+
+
+def test_c_oracle_connect_expand_equals_the_plugin_everywhere(oracle):
+    """oracle_expand against the plugin at every position of the small boards: the primitive code,
+    the children in gen_moves order (Oracle.expand sorts them, so the library is called directly)
+    and the disc count."""
+    from test_connect import SMALL, walk
+    kids = (ctypes.c_uint64 * 64)()
+    nk, pr, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    for L, H, K in SMALL:
+        w = walk(L, H, K)
+        p, n = oracle._params((L, H, K))
+        ps = list(w)
+        for pos, d in zip(ps, mcg.discs(np.array(ps, dtype=np.uint64), L, H).tolist()):
+            assert oracle.L.oracle_expand(CONNECT, p, n, pos, kids, ctypes.byref(nk), ctypes.byref(pr), ctypes.byref(t)) == 0
+            assert (pr.value, list(kids[:nk.value]), t.value) == (w[pos][0], w[pos][1], d), (L, H, K, pos)
 
 
 def test_golden_summary_counts():

@@ -13,8 +13,9 @@ forward / backward milliseconds, table bytes, positions per second of the fastes
 `--one LxH` is the child's entry: one board, one line.
 
 The default list ends at 6x5 (2.8 G positions).  The next boards up, 6x6 (69 G) and 7x5 (113 G),
-have single tiers of more than 2^31 positions, which the sparse engine's per-tier counts do not
-carry (sparse.hip batch_sort), so they are not to be run before that is widened."""
+have single tiers of more than 2^31 positions.  Such a tier is no longer sorted with a truncated
+count (sparse.hip sort_max: it skips the batch sort), but nothing else about tiers of that size
+has been tried (32-bit slot indices, table sizes), so they stay off the default list."""
 import argparse
 import json
 import os
